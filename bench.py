@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: fp64 CSR SpMV with fused shift (y = sigma*x - H x), the kernel that
 dominates the inexact-Lanczos shift-and-invert inner loop, at BASELINE.json's metric
-configuration (random-sparse Hermitian, N = 1e7, nnz/row ~ 64), plus Lanczos iterations/s
-on the same operator.
+configuration (random-sparse Hermitian, N = 1e7, nnz/row ~ 64), plus (--full) Lanczos
+iterations/s on the same operator.
 
-    python bench.py [--gpus N --steps K --warmup W]            (N > 1: starts its own N ranks, no launcher needed)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                                                               (N > 1: starts its own N ranks, no launcher needed)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W  (a launcher's RANK / WORLD_SIZE are honoured)
+
+A plain run does only what the headline figure needs: it builds the operator, warms up, times K steps, writes the
+product of the last timed step if --dump-outputs is given and prints the JSON line.  Everything else - the single-step
+spread, the per-phase times of a partitioned product, the streaming-copy rate of the device, Lanczos iterations/s,
+the block-of-8 solves and the CPU baselines - runs only with --full.
 
 One process per GPU.  With N > 1 the SAME N = 1e7 operator is row-partitioned over the ranks
 (strong scaling: total work fixed); every step is an RCCL all-gather of the operand slice
@@ -17,10 +23,16 @@ travels over a stdlib TCP exchange and barriers / max-over-ranks use the library
 all-reduce (eigensolvers_amd.distributed).
 
 Rank 0 prints ONE JSON line; `value` is whole-job algorithmic GB/s (SURVEY.md section 8d
-bytes of the GLOBAL operator x steps / max-over-ranks wall time); `roofline` prices the
-dominant kernel per GPU against the 8 TB/s HBM peak with HIP events recorded on the
-library's own stream; `cpu_baseline` times the same product through scipy's csr_matvec
-(the routine the reference's `H @ x` reaches) on a bounded row slab of the same operator.
+bytes of the GLOBAL operator x steps / max-over-ranks wall time) and `ms_per_step` the wall time
+of one timed step; `roofline` prices the dominant kernel per GPU against the 8 TB/s HBM peak with
+HIP events recorded on the library's own stream; `cpu_baseline` (--full) times the same product
+through scipy's csr_matvec (the routine the reference's `H @ x` reaches) on a bounded row slab of
+the same operator.
+
+--dump-outputs DIR writes y = sigma*x - H x of the last timed step as float64: `y.npy` while the
+N doubles fit in DUMP_MAX_VALUES, otherwise `y_sample.npy`, the rows of a fixed seeded sample
+(dump_rows); with N > 1 ranks every rank writes its share of the same rows as `<name>_rank<r>.npy`.
+The operator and x are generated from fixed seeds, so runs with the same arguments see the same inputs.
 """
 import argparse
 import json
@@ -34,6 +46,8 @@ _T_START = time.time()
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_ACHIEVABLE_GBS = 6290.0   # same guide: measured float4 copy (79 % of spec)
+DUMP_MAX_VALUES = 1 << 22     # doubles --dump-outputs writes at most: 32 MiB
+DUMP_SEED = 2024              # seed of the row sample --dump-outputs takes of a larger product
 
 
 def parse():
@@ -46,9 +60,14 @@ def parse():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--sigma", type=float, default=0.02)
     ap.add_argument("--variant", type=int, default=0, help="0 auto, 1 CSR-vector, 2 CSR-stream, 3/4 column-window blocked (wave / workgroup units), 5 = 4 with fixed-point accumulators (reproducible)")
-    ap.add_argument("--no-lanczos", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-block", action="store_true", help="skip the block-of-8 solve timing (BASELINE config #3, N = 1e6)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: single-step spread, per-phase times (N > 1 or "
+                         "HIPEIG_FORCE_COLLECTIVES), streaming-copy rate, Lanczos iterations/s, block-of-8 solves, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the product of the last step to DIR as float64 .npy (at most 32 MiB)")
+    ap.add_argument("--no-lanczos", action="store_true", help="with --full: skip the Lanczos timing")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-block", action="store_true", help="with --full: skip the block-of-8 solve timing (BASELINE config #3, N = 1e6)")
     ap.add_argument("--lanczos-L", type=int, default=8)
     ap.add_argument("--lanczos-maxit", type=int, default=4)
     ap.add_argument("--lanczos-econv", type=float, default=1e-10)
@@ -56,7 +75,10 @@ def parse():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, run the TCP rendezvous and an all-gather of the rank ids, print the JSON line, touch no GPU")
     ap.add_argument("--launch-timeout", type=float, default=3000.0, help="self-spawned ranks are stopped after this many seconds")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def kernel_signature(layout):
@@ -73,6 +95,32 @@ def kernel_signature(layout):
 
 def global_bytes(N, nnz):
     return nnz * 12 + (N + 1) * 4 + 8 * N + 8 * N
+
+
+def dump_rows(N):
+    """Global rows of y that --dump-outputs writes: None (all of them) while N <= DUMP_MAX_VALUES, otherwise a sorted
+    sample of DUMP_MAX_VALUES rows drawn with DUMP_SEED - the same rows in every run and every build of the project."""
+    import numpy as np
+    if N <= DUMP_MAX_VALUES:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(N, DUMP_MAX_VALUES, replace=False))
+
+
+def dump_outputs(directory, ctx, y, N, b, e, rank, world):
+    """y (this rank's rows [b, e) on the device) -> DIR/y.npy or DIR/y_sample.npy, float64; `_rank<r>` per rank if N > 1."""
+    import ctypes as C
+    import numpy as np
+    from eigensolvers_amd import _lib
+    host = np.empty(e - b, dtype=np.float64)
+    _lib.call("hipeig_vec_download", ctx.handle, host.ctypes.data_as(C.c_void_p), y.ptr, e - b)
+    rows = dump_rows(N)
+    name = "y"
+    if rows is not None:
+        host, name = host[rows[(rows >= b) & (rows < e)] - b], "y_sample"
+    if world > 1:
+        name += f"_rank{rank}"
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), host)
 
 
 def rendezvous_only(a, result):
@@ -200,18 +248,21 @@ def main(result):
     barrier()
     wall = allmax(time.perf_counter() - t0)
     dev_ms = allmax(dev_ms)
-    # spread of single steps (median + min), measured AFTER the timed region, one event pair per step
-    singles = []
-    for _ in range(min(a.steps, 20)):
-        ctx.timer_start()
-        H.apply_shifted(a.sigma, x._buf, y)
-        singles.append(ctx.timer_stop())
-    singles.sort()
-    step_median, step_min = allmax(singles[len(singles) // 2]), allmax(singles[0])
+    if a.dump_outputs:                     # before anything else writes y
+        dump_outputs(a.dump_outputs, ctx, y, N, b, e, rank, world)
+    if a.full:
+        # spread of single steps (median + min), measured AFTER the timed region, one event pair per step
+        singles = []
+        for _ in range(min(a.steps, 20)):
+            ctx.timer_start()
+            H.apply_shifted(a.sigma, x._buf, y)
+            singles.append(ctx.timer_stop())
+        singles.sort()
+        step_median, step_min = allmax(singles[len(singles) // 2]), allmax(singles[0])
     # where a partitioned product spends its time (events on both streams, max over ranks of the per-rank averages) and
     # what one small all-reduce of a MINRES iteration costs
     phases = None
-    if world > 1 or force:
+    if a.full and (world > 1 or force):
         ctx.phase_timing(True)
         acc = {}
         for _ in range(10):
@@ -247,17 +298,18 @@ def main(result):
             tg.barrier()
             phases["sweeps_alone_ms"] = round(allmax(alone), 5)
 
-    # what a plain streaming kernel reaches on THIS device (confirm the nominal figure on the
-    # box): out-of-place scale of 1e8 doubles, 0.8 GB read + 0.8 GB written per call, well past the Infinity Cache
-    ncopy = 100_000_000
-    ca, cb = ctx.alloc(ncopy), ctx.alloc(ncopy)
-    ea._lib.call("hipeig_vec_fill", ctx.handle, ca.ptr, ncopy, 1.0)
-    ea._lib.call("hipeig_scale", ctx.handle, ncopy, 1.0000001, ca.ptr, cb.ptr)
-    ctx.timer_start()
-    for _ in range(10):
+    if a.full:
+        # what a plain streaming kernel reaches on THIS device (confirm the nominal figure on the
+        # device): out-of-place scale of 1e8 doubles, 0.8 GB read + 0.8 GB written per call, well past the Infinity Cache
+        ncopy = 100_000_000
+        ca, cb = ctx.alloc(ncopy), ctx.alloc(ncopy)
+        ea._lib.call("hipeig_vec_fill", ctx.handle, ca.ptr, ncopy, 1.0)
         ea._lib.call("hipeig_scale", ctx.handle, ncopy, 1.0000001, ca.ptr, cb.ptr)
-    copy_gbs = -allmax(-(16.0 * ncopy / 1e9) / (ctx.timer_stop() / 10 / 1e3))     # the slowest rank's rate
-    del ca, cb
+        ctx.timer_start()
+        for _ in range(10):
+            ea._lib.call("hipeig_scale", ctx.handle, ncopy, 1.0000001, ca.ptr, cb.ptr)
+        copy_gbs = -allmax(-(16.0 * ncopy / 1e9) / (ctx.timer_stop() / 10 / 1e3))     # the slowest rank's rate
+        del ca, cb
 
     gbytes = global_bytes(N, nnz_total) / 1e9
     value = gbytes * a.steps / wall
@@ -302,21 +354,22 @@ def main(result):
                      "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "frac_of_achievable": round(achieved / HBM_ACHIEVABLE_GBS, 4), "achievable_peak": HBM_ACHIEVABLE_GBS,
-                     "measured_stream_GBs": round(copy_gbs, 1), "frac_of_measured_stream": round(achieved / copy_gbs, 4),
                      "traffic": traffic,
                      "traffic_source": "profiles/pmc_current.json (separate rocprofv3 --pmc passes)" if traffic else traffic_note,
                      "kernel_signature": signature,
                      "launches_per_step": nlaunch,
                      "algorithmic_bytes_per_launch": int(H.algorithmic_bytes() // nlaunch),
                      "avg_launch_ms": round(dev_ms / a.steps / nlaunch, 5),
-                     "ms_per_step_device": round(dev_ms / a.steps, 5),
-                     "single_step_ms_median": round(step_median, 5), "single_step_ms_min": round(step_min, 5)},
+                     "ms_per_step_device": round(dev_ms / a.steps, 5)},
     }
+    if a.full:
+        out["roofline"].update({"measured_stream_GBs": round(copy_gbs, 1), "frac_of_measured_stream": round(achieved / copy_gbs, 4),
+                                "single_step_ms_median": round(step_median, 5), "single_step_ms_min": round(step_min, 5)})
     if phases is not None:
         out["phases"] = phases
 
     # ---- Lanczos iterations/s on the same operator (outside the timed SpMV region) ----
-    if not a.no_lanczos:
+    if a.full and not a.no_lanczos:
         opts = {"linearSystemArgs": {"linearSolver": "minres", "linearIter": 2000, "linear_tol": 1e-10}}
         from eigensolvers_amd.generators import guess_vector
         v0 = ea.HipVector(guess_vector(N, 1, b, e).copy(), opts, ctx=ctx)
@@ -339,7 +392,7 @@ def main(result):
                           "L": a.lanczos_L, "maxit": a.lanczos_maxit, "eConv": a.lanczos_econv, "linear_tol": 1e-10}
 
     # ---- BASELINE config #3 (N = 1e6, 32 nnz/row, block of 8): lock-step block solve vs eight single solves ----
-    if world == 1 and not a.no_block:
+    if a.full and world == 1 and not a.no_block:
         Nb = 1_000_000
         Hb = ea.HipCsrOperator.generate(Nb, 32, seed=a.seed, ctx=ctx)
         Qb = np.random.default_rng(5).standard_normal((Nb, 8))
@@ -375,7 +428,7 @@ def main(result):
         del Hb, Xb, Wb, Sb
 
     # ---- CPU baseline: scipy csr_matvec on a bounded row slab (rank 0, single GPU only) ----
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         rows = min(N, max(1000, int(2.0e7 // max(a.nnz_row, 1))))     # ~2e7 non-zeros
         slab = ea.HipCsrOperator.generate(N, a.nnz_row, seed=a.seed, row_begin=0, row_end=rows, ctx=ctx).to_scipy()
         xh = np.random.default_rng(100).standard_normal(N)

@@ -153,7 +153,7 @@ def test_bench_started_plainly_with_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HIPEIG_COMM"] = "direct"
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--n", "2000000", "--steps", "5",
-                        "--warmup", "2", "--no-cpu"], capture_output=True, text=True, env=env, timeout=800)
+                        "--warmup", "2", "--full", "--no-cpu"], capture_output=True, text=True, env=env, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

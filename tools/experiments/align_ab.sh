@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out
 for al in 0 1 0 1; do
   echo "== HIPEIG_TCOOW_ALIGN=$al"
-  HIPEIG_TCOOW_ALIGN=$al timeout -k 10 200 python3 $R/bench.py --steps 30 --warmup 5 --no-cpu --no-lanczos --no-block 2>/dev/null | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], "ms/step frac", d["roofline"]["frac"], "median", d["roofline"]["single_step_ms_median"])'
+  HIPEIG_TCOOW_ALIGN=$al timeout -k 10 200 python3 $R/bench.py --steps 30 --warmup 5 --full --no-cpu --no-lanczos --no-block 2>/dev/null | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], "ms/step frac", d["roofline"]["frac"], "median", d["roofline"]["single_step_ms_median"])'
 done
 cd /tmp && export TMPDIR=/tmp
 for al in 0 1; do

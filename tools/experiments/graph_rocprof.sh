@@ -38,8 +38,8 @@ run() {  # tag, rocprof flags, env..., -- args
 }
 export HIPEIG_GRAPH_TRACE=1
 ENVS="PRE_GRAM=1" run e9_1e7_pregram "--kernel-trace" 10000000 64
-echo "== e10: bench.py --no-cpu --no-block, HIPEIG_GRAPH=1 HIPEIG_GRAPH_TRACE=1, rocprofv3 --kernel-trace" > $O/graph2_e10_bench_trace.txt
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/graph2_prof_e10 -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu --no-block >> $O/graph2_e10_bench_trace.txt 2>&1
+echo "== e10: bench.py --full --no-cpu --no-block, HIPEIG_GRAPH=1 HIPEIG_GRAPH_TRACE=1, rocprofv3 --kernel-trace" > $O/graph2_e10_bench_trace.txt
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/graph2_prof_e10 -- python3 $R/bench.py --steps 5 --warmup 1 --full --no-cpu --no-block >> $O/graph2_e10_bench_trace.txt 2>&1
 echo "rc=$?" >> $O/graph2_e10_bench_trace.txt; grep -E "hipeig graph|^rc=" $O/graph2_e10_bench_trace.txt | tail -8
 else
 # Hypothesis test (one run each): the abort needs a few hundred replays of a captured graph (the AQL queue

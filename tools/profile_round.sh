@@ -6,7 +6,7 @@
 TAG=${1:-r01}
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -- python3 $R/bench.py > $O/prof_$TAG.log 2>&1      # the default command, as the driver runs it
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -- python3 $R/bench.py --full > $O/prof_$TAG.log 2>&1      # every measured path, the solver kernels included
 tail -1 $O/prof_$TAG.log | cut -c1-300
 for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "l2:TCC_HIT_sum TCC_MISS_sum"; do
   name=${pass%%:*}; ctr=${pass#*:}
