@@ -655,8 +655,8 @@ tcoow_bin_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__
       const uint32_t cc = (uint32_t)col[p];
       const uint32_t slot = atomicAdd(cur + (cc >> binbits), 1u);
       if (fill) {
-        w_idx[slot] = (rl << wbits) | (cc & wmask);
-        w_val[slot] = val[p];
+        w_idx[tcoow_islot(slot)] = (rl << wbits) | (cc & wmask);      // lane-major inside its 256-slot batch
+        w_val[tcoow_vslot(slot)] = val[p];
       }
     }
   }
@@ -735,13 +735,19 @@ static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair) {
   // by exactly ONE gather instruction of one wave: L1 -> L2 read requests per launch 1.829e8 -> 1.704e8, i.e. gather fills
   // per non-zero 0.468 -> 0.431 against the ideal (1 - exp(-k))/k = 0.426, and 2.083 -> 1.90 ms per product at N = 1e7
   // (profiles/r03_spmv_aligned_bins.txt).  HIPEIG_TCOOW_ALIGN=0 restores the unaligned stream.
+  // Whatever the knob, every stream range a wave can start on begins on a 256-slot batch (the sweep loads batches
+  // lane-major, tcoow_islot / tcoow_vslot): unit starts, and on a row-partitioned operator every window start, since any window can
+  // begin a run of the overlapped plan (hipeig_tcoow_plan).  Column-split shares are cut at batch multiples.
   const char* al_env = getenv(pair ? "HIPEIG_TCOOW_PAIR_ALIGN" : "HIPEIG_TCOOW_ALIGN");
   const bool align = !(al_env && atoi(al_env) == 0);
+  const bool win_batches = A->col_stride > 0;
   uint64_t run = 0, counted = 0;
   for (size_t i = 0; i < ncnt; ++i) {
     if (i % bpw == 0) {
-      if (align) run = (run + 63) & ~(uint64_t)63;
-      off[i / bpw] = (uint32_t)run;
+      const size_t tile = i / bpw;
+      if (tile % nwin == 0 || win_batches) run = (run + TCOOW_BATCH - 1) & ~(uint64_t)(TCOOW_BATCH - 1);
+      else if (align) run = (run + 63) & ~(uint64_t)63;
+      off[tile] = (uint32_t)run;
     }
     const uint32_t n = cnt[i];
     if (align && n > 0 && n <= 64 && (run & 63) + n > 64) run = (run + 63) & ~(uint64_t)63;
@@ -751,8 +757,9 @@ static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair) {
   }
   off[ntile] = (uint32_t)run;
   HIPEIG_REQUIRE(counted == (uint64_t)A->nnz, "TCOO-W count pass lost non-zeros");
-  HIPEIG_REQUIRE(run < ((uint64_t)1 << 32), "blocked stream too long for 32-bit offsets");
-  const size_t nslots = (size_t)run;                   // stream length incl. padding (== nnz without alignment)
+  const uint64_t padded = (run + TCOOW_BATCH - 1) & ~(uint64_t)(TCOOW_BATCH - 1);     // the last batch is loaded whole
+  HIPEIG_REQUIRE(padded < ((uint64_t)1 << 32), "blocked stream too long for 32-bit offsets");
+  const size_t nslots = (size_t)padded;                // stream length incl. padding slots
   HIPEIG_CHECK(hipMemcpyAsync(d_cur, cnt.data(), ncnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   uint32_t*& l_off = pair ? A->p_off : A->w_off;       // owned by the operator from the allocation on
   uint32_t*& l_idx = pair ? A->p_idx : A->w_idx;
@@ -763,8 +770,8 @@ static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair) {
     // occupy L2 lines / tag bandwidth next to the x window
     const char* uc = getenv("HIPEIG_TCOOW_UNCACHED");
     if (uc && atoi(uc) != 0) {
-      HIPEIG_CHECK(hipExtMallocWithFlags((void**)&l_idx, (size_t)A->nnz * sizeof(uint32_t), hipDeviceMallocUncached));
-      HIPEIG_CHECK(hipExtMallocWithFlags((void**)&l_val, (size_t)A->nnz * sizeof(double), hipDeviceMallocUncached));
+      HIPEIG_CHECK(hipExtMallocWithFlags((void**)&l_idx, nslots * sizeof(uint32_t), hipDeviceMallocUncached));
+      HIPEIG_CHECK(hipExtMallocWithFlags((void**)&l_val, nslots * sizeof(double), hipDeviceMallocUncached));
     } else {
       HIPEIG_CHECK(hipMalloc((void**)&l_idx, nslots * sizeof(uint32_t)));
       HIPEIG_CHECK(hipMalloc((void**)&l_val, nslots * sizeof(double)));
@@ -986,14 +993,16 @@ extern "C" int hipeig_csr_destroy(hipeig_ctx* c, hipeig_csr* A) {
 // Layout constants of the blocked copy the product runs on (what a committed counter profile is only valid for):
 // out[0] = kernel variant of the last launch, [1] rows per row block, [2] window bits, [3] row blocks, [4] windows,
 // [5] column splits, [6] workgroups per sweep launch, [7] threads per workgroup, [8] batch unroll, [9] chunks of the
-// operand exchange, [10] rows per (rank, chunk) of the gathered layout (0: not partitioned)
-extern "C" int hipeig_csr_layout_info(hipeig_csr* A, int64_t out[12]) {
-  memset(out, 0, 12 * sizeof(int64_t));
+// operand exchange, [10] rows per (rank, chunk) of the gathered layout (0: not partitioned), [11] bins, [12] stream
+// slots incl. padding (TCOO-W)
+extern "C" int hipeig_csr_layout_info(hipeig_csr* A, int64_t out[13]) {
+  memset(out, 0, 13 * sizeof(int64_t));
   out[0] = A->last_variant;
   if (A->last_variant == 4 || A->last_variant == 5) {
     out[1] = A->w_rw; out[2] = A->w_wbits; out[3] = A->w_nunits; out[4] = A->w_nwin; out[5] = A->w_csplit;
     out[6] = A->w_wgs_per_sweep; out[7] = TCOOW_THREADS; out[8] = TCOO_UNROLL;
     out[11] = A->w_binbits + 100 * A->w_align;
+    out[12] = A->w_slots;
   } else if (A->last_variant == 3) {
     out[1] = A->t_rw; out[2] = A->t_wbits; out[3] = A->t_nunits; out[4] = A->t_nwin; out[6] = A->t_wgs_per_sweep;
     out[7] = HIPEIG_BLOCK; out[8] = TCOO_UNROLL;

@@ -126,9 +126,6 @@ __device__ __forceinline__ void csr_vector_sweep(const CsrView& A, const double*
 #ifndef TCOO_UNROLL
 #define TCOO_UNROLL 4
 #endif
-#ifndef TCOOW_INTERLEAVE
-#define TCOOW_INTERLEAVE 0   // 1: the waves of a workgroup take adjacent 64-element groups (instruction-level interleave)
-#endif
 
 // Timing experiments (skip gathers / LDS adds / the value stream / window switching) are compiled
 // in only with -DHIPEIG_EXPERIMENTS (make EXPERIMENTS=1); the shipped kernels carry none of it.
@@ -276,6 +273,26 @@ __device__ __forceinline__ void tcoo_sweep(const TcooView& T, const double* __re
 #define TCOOW_MAX_WIN 256
 #define HIPEIG_TCOOW_LDS_MAX ((size_t)TCOOW_MAX_RW * sizeof(double) + (TCOOW_MAX_WIN + 2) * sizeof(uint32_t))
 
+// Stream positions of slot s = B + lane + 64*j (B a multiple of 256) of a TCOO-W layout: the batch is stored lane-major,
+// the index at B + 4*lane + j and the value at B + 128*(j/2) + 2*lane + j%2, so that the sweep loads a lane's four
+// indices with one 16-byte load and its four values with two, and every one of these three wave instructions reads
+// 1 KiB of consecutive bytes (values at B + 4*lane + j instead: each value instruction touches 16 lines, half of each,
+// and the second one the same lines again: 2.55 against 2.48 ms per product at N = 1e7 in a build that waited for the
+// stream loads right after issuing them, EXPERIMENTS.md R5-stream).
+// Every range a wave starts on (unit starts, run starts, column-split shares) is a multiple of 256.
+#define TCOOW_BATCH 256
+#if defined(TCOOW_INTERLEAVE) && TCOOW_INTERLEAVE
+#error "TCOOW_INTERLEAVE (waves on adjacent 64-element groups) does not match the lane-major TCOO-W stream"
+#endif
+__host__ __device__ __forceinline__ uint32_t tcoow_islot(uint32_t s) {
+  return (s & ~255u) | ((s & 63u) << 2) | ((s >> 6) & 3u);
+}
+__host__ __device__ __forceinline__ uint32_t tcoow_vslot(uint32_t s) {
+  return (s & ~255u) | ((s & 128u) >> 0) | ((s & 63u) << 1) | ((s >> 6) & 1u);
+}
+typedef uint32_t tcoow_u32x4 __attribute__((ext_vector_type(4)));
+typedef double tcoow_f64x2 __attribute__((ext_vector_type(2)));
+
 __device__ __forceinline__ void lds_add_f64_wg(double* p, double v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -385,34 +402,39 @@ __device__ __forceinline__ void tcoo_wg_sweep(const TcooView& T, const double* _
   // walking the offsets (they only move forward), so a batch may straddle windows and the
   // stream loads of batch k+1 are in flight while batch k gathers and scatters.
   const uint32_t step = (uint32_t)nw * 64 * TCOO_UNROLL;
-#if TCOOW_INTERLEAVE
-  // element j of a batch: the 16 waves cover adjacent 64-element groups at every j, so the
-  // whole CU works on one narrow column range at a time (L1 reuse across waves)
-  const uint32_t jstride = (uint32_t)nw * 64;
-  const uint32_t wave_off = (uint32_t)wid * 64;
-#else
+  // Element q = B + lane + 64*j of a batch (B a multiple of 256) is stored lane-major (tcoow_islot / tcoow_vslot):
+  // a lane's four indices are one 16-byte load and its four values two, where the element-major order took four
+  // 4-byte and four 8-byte loads.  Which elements share a gather instruction is unchanged.
+  static_assert(TCOO_UNROLL == 4, "the lane-major stream of the TCOO-W layout holds 4 elements per lane and batch");
   const uint32_t jstride = 64;
   const uint32_t wave_off = (uint32_t)wid * 64 * TCOO_UNROLL;
-#endif
   int c = 0;
   double sink = 0.0;
   uint32_t idA[TCOO_UNROLL], idB[TCOO_UNROLL];
   double vA[TCOO_UNROLL], vB[TCOO_UNROLL];
 #define TCOO_LOAD(ID, V, BASE)                                                         \
-  _Pragma("unroll") for (int j = 0; j < TCOO_UNROLL; ++j) {                            \
-    const uint32_t q = (BASE) + lane + jstride * j;                                         \
-    const bool ok = q < send;                                                          \
+  {                                                                                    \
     /* experiment bit 16: the stream re-reads the unit's first 4096 elements (L2-resident stream: what a perfect */ \
-    /* prefetch of the stream into L2 could buy; wrong results)                                                  */ \
-    const uint32_t ql = (TCOO_ABL(T, 16)) ? sbeg + ((q - sbeg) & 4095u) : q;           \
-    ID[j] = ok ? __builtin_nontemporal_load(T.idx + ql) : 0xFFFFFFFFu;                 \
-    V[j] = (ok && !(TCOO_ABL(T, 4))) ? __builtin_nontemporal_load(T.val + ql) : 1.0;    \
+    /* prefetch of the stream into L2 could buy; wrong results) - whole batches, so the layout stays lane-major  */ \
+    const uint32_t bl = (TCOO_ABL(T, 16)) ? sbeg + (((BASE) - sbeg) & 4095u) : (BASE);  \
+    /* unconditional: a batch begins below send and every allocation ends on a batch boundary; lanes past send */ \
+    /* are masked in TCOO_CONSUME (a select here would wait for the loads right after issuing them)            */ \
+    const tcoow_u32x4 iv = __builtin_nontemporal_load(reinterpret_cast<const tcoow_u32x4*>(T.idx + (size_t)bl + 4 * lane)); \
+    tcoow_f64x2 v01 = {1.0, 1.0}, v23 = {1.0, 1.0};                                   \
+    if (!(TCOO_ABL(T, 4))) {                                                           \
+      const double* vb = T.val + (size_t)bl + 2 * lane;                                \
+      v01 = __builtin_nontemporal_load(reinterpret_cast<const tcoow_f64x2*>(vb));       \
+      v23 = __builtin_nontemporal_load(reinterpret_cast<const tcoow_f64x2*>(vb + 128)); \
+    }                                                                                  \
+    ID[0] = iv.x; ID[1] = iv.y; ID[2] = iv.z; ID[3] = iv.w;                            \
+    V[0] = v01.x; V[1] = v01.y; V[2] = v23.x; V[3] = v23.y;                            \
   }
 #define TCOO_CONSUME(ID, V, BASE)                                                      \
   {                                                                                    \
     int cw[TCOO_UNROLL];                                                               \
     _Pragma("unroll") for (int j = 0; j < TCOO_UNROLL; ++j) {                          \
       const uint32_t q = (BASE) + lane + jstride * j;                                       \
+      if (!(q < send)) ID[j] = 0xFFFFFFFFu;          /* past the range: a lane of a partial batch */ \
       /* padding lanes (q >= send) must not move the cursor: it would run into the windows skipped  */ \
       /* between two runs and the next run's first elements would gather from there                */ \
       while (q < send && c + 1 < T.nwin && q >= offL[c + 1]) ++c;                      \
@@ -461,10 +483,10 @@ __device__ __forceinline__ void tcoo_wg_sweep(const TcooView& T, const double* _
   for (int part = 0; part < nparts; ++part) {
     uint32_t sbeg = T.nrun ? offL[T.run_lo[part]] : offL[0];
     uint32_t send = T.nrun ? offL[T.run_hi[part]] : offL[T.nwin];
-    if (T.csplit > 1) {                              // this workgroup's share of the range (64-element granules)
+    if (T.csplit > 1) {                              // this workgroup's share of the range (whole 256-element batches)
       const uint64_t len = send - sbeg;
-      const uint32_t b0 = sbeg + (uint32_t)((len * (uint64_t)cs / (uint64_t)T.csplit) & ~(uint64_t)63);
-      const uint32_t b1 = (cs + 1 == T.csplit) ? send : sbeg + (uint32_t)((len * (uint64_t)(cs + 1) / (uint64_t)T.csplit) & ~(uint64_t)63);
+      const uint32_t b0 = sbeg + (uint32_t)((len * (uint64_t)cs / (uint64_t)T.csplit) & ~(uint64_t)255);
+      const uint32_t b1 = (cs + 1 == T.csplit) ? send : sbeg + (uint32_t)((len * (uint64_t)(cs + 1) / (uint64_t)T.csplit) & ~(uint64_t)255);
       sbeg = b0; send = b1;
     }
     uint32_t base = sbeg + wave_off;

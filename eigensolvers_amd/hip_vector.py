@@ -347,11 +347,14 @@ class HipCsrOperator:
 
     def layout_info(self):
         """Layout constants of the blocked copy the last product ran on (a counter profile is valid for these only)."""
-        out = (C.c_int64 * 12)()
+        out = (C.c_int64 * 13)()
         _lib.call("hipeig_csr_layout_info", self.handle, out)
         keys = ("variant", "rows_per_block", "window_bits", "row_blocks", "windows", "column_splits", "workgroups_per_launch",
                 "threads", "unroll", "exchange_chunks", "rows_per_rank_chunk", "bins")
-        return {k: int(out[i]) for i, k in enumerate(keys)}
+        info = {k: int(out[i]) for i, k in enumerate(keys)}
+        if out[12] > 0:                    # workgroup-unit stream: slots (padding included) per non-zero
+            info["padding"] = round(int(out[12]) / max(1, self.nnz), 5)
+        return info
 
     def launches_per_apply(self):
         """Kernel launches (sweeps) one product takes with the variant last used."""
