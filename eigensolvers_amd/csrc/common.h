@@ -141,6 +141,49 @@ struct hipeig_ctx {
   int exchange_off;          // measurement aid (hipeig_comm_set_exchange): products place the own slice and skip the exchange
 };
 
+// One blocked copy of the operator (TCOO, TCOO-W, the pair copy of TCOO-W, TCOO-B): the local rows cut into units of
+// `rw` rows, the columns into windows of 2^wbits; the non-zeros of (unit, window) tile t, stored as
+// uint32 (row_local << wbits | col_local) + fp64, start at slot off[t] of the stream.
+struct BlockedLayout {
+  uint32_t* idx;
+  double* val;
+  uint32_t* off;             // nunits * nwin + 1 offsets, unit-major
+  int32_t nunits, nwin, wbits, rw;
+  int32_t wgs_per_sweep;     // workgroups one sweep launch holds
+  int32_t csplit;            // workgroups sharing one unit (column splits, TCOO-W), <= 1 = none
+  int32_t binbits, align;    // columns per bin (log2) and whether bins are kept inside 64-slot instruction groups
+  int64_t slots;             // stream length incl. padding slots
+  int32_t state;             // TCOO-B: 0 = undecided, 1 = built, 2 = not suited (row-owner kernel is used)
+};
+
+// Dynamic LDS of a workgroup-unit sweep (TCOO-W: 1 accumulator per row, its pair copy: 2, TCOO-B: K): the accumulators
+// and the unit's window offsets.
+static inline size_t blocked_lds_bytes(const BlockedLayout& L, int acc_per_row) {
+  return (size_t)L.rw * acc_per_row * sizeof(double) + ((size_t)L.nwin + 2) * sizeof(uint32_t);
+}
+
+// Workgroups per sweep launch and sweep launches per product of a blocked copy whose workgroups take `units_per_wg`
+// units each (TCOO: 4 wave units; the others one unit, or with column splits one share of one).  A launch holds
+// wgs_per_sweep workgroups, a column-split sweep all of them, never more than HIPEIG_MAX_PARTIALS; launch i starts at
+// workgroup i * wgs.
+struct SweepGrid { int wgs, launches; };
+static inline SweepGrid blocked_grid(const BlockedLayout& L, int units_per_wg = 1) {
+  const int64_t total = L.csplit > 1 ? (int64_t)L.nunits * L.csplit : ((int64_t)L.nunits + units_per_wg - 1) / units_per_wg;
+  int64_t g = (L.csplit > 1 || total < L.wgs_per_sweep) ? total : L.wgs_per_sweep;
+  if (g < 1) g = 1;
+  if (g > HIPEIG_MAX_PARTIALS) g = HIPEIG_MAX_PARTIALS;
+  return SweepGrid{(int)g, (int)((total + g - 1) / g)};
+}
+
+// Padding and slot policy of a binned copy (hipeig_build_binned)
+enum : unsigned {
+  BIN_LANE_MAJOR = 1,        // slots lane-major inside their 256-slot batch (tcoow_islot / tcoow_vslot); else in order
+  BIN_UNIT_BATCH = 2,        // every unit starts on a batch and the stream ends on one
+  BIN_GROUP_ALIGN = 4,       // tiles start on a 64-slot group and no bin of <= 64 slots straddles one
+  BIN_WIN_BATCH = 8,         // every tile (window) starts on a batch: any window can begin a run (remapped columns)
+  BIN_UNCACHED = 16,         // stream in uncached device memory (experiment knob)
+};
+
 struct hipeig_csr {
   int64_t nrows, ncols, nnz, row_offset;
   int32_t* d_rowptr;         // nrows+1
@@ -148,36 +191,17 @@ struct hipeig_csr {
   double* d_val;             // nnz
   int32_t* d_row_blocks;     // n_row_blocks+1 row indices: block b owns rows [rb[b], rb[b+1])
   int32_t n_row_blocks;
-  // column-window blocked copy (see spmv_device.h, "TCOO"); built on first use
-  uint32_t* t_idx;
-  double* t_val;
-  uint32_t* t_off;
-  int32_t t_nunits, t_nwin, t_wbits, t_rw, t_wgs_per_sweep, t_prefetch;
-  // workgroup-wide column-bucketed copy ("TCOO-W", variant 4); built on first use
-  uint32_t* w_idx;
-  double* w_val;
-  uint32_t* w_off;
-  int32_t w_nunits, w_nwin, w_wbits, w_rw, w_wgs_per_sweep;
-  int32_t w_csplit;          // workgroups sharing one row block (column splits), 1 = none
-  int32_t w_binbits, w_align; // columns per bin (log2) and whether bins are aligned to 64-element instruction groups
-  int64_t w_slots;           // stream length incl. padding slots (== nnz without alignment)
-  // copy of the same layout for the pair sweep (two accumulators per row: units of half the rows), built
-  // on the first hipeig_spmv_shift_pair of a large operator
-  uint32_t* p_idx;
-  double* p_val;
-  uint32_t* p_off;
-  int32_t p_nunits, p_nwin, p_wbits, p_rw, p_wgs_per_sweep;
+  // blocked copies, each built on first use:
+  BlockedLayout t;           // column-window copy with wave-owned rows ("TCOO", variant 3, spmv_device.h)
+  int32_t t_prefetch;        // TCOO only: dense L2 prefetch of the next window
+  BlockedLayout w;           // workgroup-wide column-bucketed copy ("TCOO-W", variants 4 / 5)
+  BlockedLayout p;           // the same for the pair sweep (two accumulators per row: units of half the rows), built
+                             // on the first hipeig_spmv_shift_pair of a large operator
+  BlockedLayout b[3];        // block-operand copies ("TCOO-B", spmm_device.h), one per interleave width: K = 4, 8, 16
+                             // (b[layout_slot(K)])
   int32_t last_pair_fused;   // 1 when the most recent pair product ran as one sweep
   int reproducible;          // automatic choice restricted to bitwise reproducible kernels (hipeig_csr_set_reproducible)
   double absrow_max;         // max_i sum_j |a_ij| over the local rows: overflow bound of the fixed-point sweep (variant 5)
-  // block-operand copies ("TCOO-B", spmm_device.h): one per interleave width, [0]: K = 4, [1]: K = 8, [2]: K = 16; built on first use
-  struct BcooLayout {
-    uint32_t* idx;
-    double* val;
-    uint32_t* off;
-    int32_t nunits, nwin, wbits, rw, wgs_per_sweep;
-    int32_t state;           // 0 = undecided, 1 = built, 2 = not suited (row-owner kernel is used)
-  } bl[3];
   int32_t block_variant;     // 0 = automatic, 1 = row-owner CSR, 2 = TCOO-B
   int32_t last_block_variant, last_block_k;
   int64_t gather_len;        // length of the gathered operand (ncols, or gl.total())
@@ -189,6 +213,16 @@ struct hipeig_csr {
   int64_t col_stride;        // > 0 when the columns were remapped to the gathered layout `gl` (= gl.h); 0 = global columns
   int64_t bytes;
 };
+
+static inline int layout_slot(int K) { return K == 4 ? 0 : K == 8 ? 1 : 2; }
+
+// Build a binned copy (TCOO-W, its pair copy, TCOO-B) of the geometry in `geom` (rw, wbits, binbits, nunits, nwin; the
+// caller's other fields are copied through): count the non-zeros per (unit, bin), scan on the host with the padding of
+// `policy`, allocate, scatter.  On success *out receives the copy and its stream joins A->bytes.  Returns 1 on a failure
+// (error set) and 2 when the copy does not fit its counters or 32-bit offsets; either way nothing stays allocated and
+// *out is left as it was.
+int hipeig_build_binned(hipeig_ctx* c, hipeig_csr* A, const BlockedLayout& geom, unsigned policy, BlockedLayout* out);
+void hipeig_free_layout(BlockedLayout* L);
 
 // Synchronise the compute stream and report a direct-exchange wait that gave up (comm_direct.hip): every path that hands
 // a result to the host goes through this, so a timed-out wait is an error of THAT call, not of some later one.

@@ -26,14 +26,12 @@
 #include "spmv_device.h"
 
 CsrView hipeig_csr_view(const hipeig_csr* A);
-TcooView hipeig_tcoo_view(const hipeig_csr* A);
-TcooView hipeig_tcoow_view(const hipeig_csr* A);
-size_t hipeig_tcoow_lds_bytes(const hipeig_csr* A);
+TcooView hipeig_tcoo_view(const hipeig_csr* A, const BlockedLayout& L);
 int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, int fixed, TcooView* last, bool* has_last,
                           const double** xg, int* ncombine);
 int64_t hipeig_tcoow_part_stride(const hipeig_csr* A);
 int hipeig_tcoow_reserve(hipeig_ctx* c, const hipeig_csr* A);
-int hipeig_spmv_grid(const hipeig_csr* A, int variant);
+SweepGrid hipeig_sweep_grid(const hipeig_csr* A, int variant);
 int hipeig_csr_pick_variant(hipeig_ctx* c, hipeig_csr* A);
 size_t hipeig_tcoo_lds_bytes(const hipeig_csr* A);
 void hipeig_phase_mark(hipeig_ctx* c, int k);
@@ -321,7 +319,9 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
   if (fixed) variant = 4;
   if (variant == 4 && hipeig_tcoow_reserve(c, A)) return 1;
   const CsrView view = hipeig_csr_view(A);
-  const TcooView tview = (variant == 4) ? hipeig_tcoow_view(A) : hipeig_tcoo_view(A);
+  const BlockedLayout& L = (variant == 4) ? A->w : A->t;    // the blocked copy of variants 3 / 4
+  const TcooView tview = hipeig_tcoo_view(A, L);
+  const size_t ldsA = (variant == 4) ? blocked_lds_bytes(A->w, 1) : (variant == 3) ? hipeig_tcoo_lds_bytes(A) : 0;
   if (variant == 4) {
     HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_ka_kernel<4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_TCOOW_LDS_MAX));
     HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_ka_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_TCOOW_LDS_MAX));
@@ -329,7 +329,8 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
   if (variant == 3)
     HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_ka_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)HIPEIG_TCOO_LDS_MAX));
-  const int gA = hipeig_spmv_grid(A, variant);
+  const SweepGrid sgA = hipeig_sweep_grid(A, variant);
+  const int gA = sgA.wgs, nsweepA = sgA.launches;
   int per_thread = 24;       // measured (tools/experiments/mr_grid_sweep.sh): 4 / 8 / 16 / 24 / 32 / 64 elements per thread -> 0.138 / 0.136 / 0.134 / 0.1335 / 0.135 / 0.140 ms per iteration at N = 1e6, 2.32 / 2.24 / 2.23 / 2.21 / 2.22 / 2.20 at N = 1e7: the fixed cost of a workgroup (state record, ticket), not the grid cap, is what these kernels feel
   if (const char* e = getenv("HIPEIG_MR_PER_THREAD")) per_thread = atoi(e) > 0 ? atoi(e) : 24;     // tuning knob
   const int gE = grid_wide(n, per_thread);                   // element-wise kernels: their reductions finish in the last workgroup
@@ -344,10 +345,7 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
   const bool dist = c->collectives != 0;
   MinresArgs a;
   a.sigma = sigma; a.sign = sign; a.rtol = rtol; a.maxiter = maxiter;
-  const bool split = (variant == 4) && A->w_csplit > 1;      // raw slabs + combine launch
-  const int nsweepA = split ? 1 : (variant == 4) ? (A->w_nunits + gA - 1) / gA
-                    : (variant == 3) ? (A->t_nunits + gA * 4 - 1) / (gA * 4) : 1;
-  HIPEIG_REQUIRE(nsweepA * gA <= HIPEIG_WIDE_PARTIALS, "too many sweeps for the partial-sum buffer");
+  const bool split = (variant == 4) && A->w.csplit > 1;      // raw slabs + combine launch
   // combine launch of a column-split sweep (slab of a many-GPU run): rows per thread.  It carries the whole KA epilogue with
   // the riding KD (10 streams + the slabs), not a 2-stream update: 24 / 12 / 8 / 4 / 2 rows per thread -> 0.177 / 0.160 /
   // 0.156 / 0.160 / 0.166 ms per iteration (N = 1e6, 5 splits forced; profiles/r04_minres_combine_grid.txt)
@@ -355,6 +353,7 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
   if (const char* e = getenv("HIPEIG_MR_COMBINE_PER_THREAD")) ct = atoi(e) > 0 ? atoi(e) : 8;   // tuning knob
   const int gC = grid_wide(n, ct);
   const int nPA = split ? gC : gA * nsweepA;                 // partial <v,y> sums one iteration leaves in pA
+  HIPEIG_REQUIRE(nPA <= HIPEIG_WIDE_PARTIALS, "too many sweeps for the partial-sum buffer");
   a.pA = tot + 0; a.nA = 1;
   a.pD = tot + 1; a.nD = 1;
   a.pC = tot + 2; a.nC = 1; a.sC = 0;
@@ -394,8 +393,8 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
       if (has_last) {
         for (int sw = 0; sw < nsweepA; ++sw) {
           tv.unit_begin = sw * gA;
-          if (fixed) KA_LAUNCH(4, 1, gA, TCOOW_THREADS, hipeig_tcoow_lds_bytes(A), tv, sw * gA);
-          else KA_LAUNCH(4, 0, gA, TCOOW_THREADS, hipeig_tcoow_lds_bytes(A), tv, sw * gA);
+          if (fixed) KA_LAUNCH(4, 1, gA, TCOOW_THREADS, ldsA, tv, sw * gA);
+          else KA_LAUNCH(4, 0, gA, TCOOW_THREADS, ldsA, tv, sw * gA);
         }
       }
       if (ncombine) {
@@ -412,7 +411,7 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
     if (variant == 3) {
       for (int sw = 0; sw < nsweepA; ++sw) {       // one launch per sweep; partials side by side
         tv.unit_begin = sw * gA * 4;
-        KA_LAUNCH(3, 0, gA, HIPEIG_BLOCK, hipeig_tcoo_lds_bytes(A), tv, sw * gA);
+        KA_LAUNCH(3, 0, gA, HIPEIG_BLOCK, ldsA, tv, sw * gA);
       }
     } else if (variant == 1) {
       KA_LAUNCH(1, 0, gA, HIPEIG_BLOCK, 0, tview, 0);
@@ -499,11 +498,11 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
     } key;
     memset(&key, 0, sizeof(key));
     key.A = A; key.rowptr = A->d_rowptr; key.col = A->d_col; key.val = A->d_val;
-    key.tidx = A->t_idx; key.widx = A->w_idx; key.ws = c->mr_ws; key.state = V; key.parts = c->ytmp;
+    key.tidx = A->t.idx; key.widx = A->w.idx; key.ws = c->mr_ws; key.state = V; key.parts = c->ytmp;
     key.n = n; key.nnz = A->nnz; key.variant = variant; key.gA = gA; key.nsweep = nsweepA;
-    key.units = (variant == 4) ? A->w_nunits : (variant == 3) ? A->t_nunits : A->n_row_blocks;
-    key.lds = (variant == 4) ? (int64_t)hipeig_tcoow_lds_bytes(A) : (variant == 3) ? (int64_t)hipeig_tcoo_lds_bytes(A) : 0;
-    key.csplit = (variant == 4) ? A->w_csplit + (fixed ? 1000 : 0) : 0;
+    key.units = (variant >= 3) ? L.nunits : A->n_row_blocks;
+    key.lds = (int64_t)ldsA;
+    key.csplit = (variant == 4) ? A->w.csplit + (fixed ? 1000 : 0) : 0;
     key.maxiter = maxiter; key.sigma = sigma; key.sign = sign; key.rtol = rtol;
     key.csplit += fuse_kd ? 100000 : 0;
     const int gchunk = 18;

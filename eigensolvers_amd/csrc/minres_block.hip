@@ -16,9 +16,7 @@
 #include "spmm_device.h"
 
 int hipeig_block_pick_variant(hipeig_ctx* c, hipeig_csr* A, int K, int for_solve);
-BcooView hipeig_bcoo_view(const hipeig_csr* A, int K);
-size_t hipeig_bcoo_lds_bytes(const hipeig_csr* A, int K);
-int hipeig_bcoo_grid(const hipeig_csr* A, int K);
+BcooView hipeig_bcoo_view(const hipeig_csr* A, const BlockedLayout& L);
 int hipeig_block_allgather(hipeig_ctx* c, hipeig_csr* A, int K, const double* xb_local, const double** xb_full);
 int hipeig_block_pack(hipeig_ctx* c, int K, int64_t n, int k, const double* const* cols, double* blk);
 int hipeig_block_unpack(hipeig_ctx* c, int K, int64_t n, int k, const double* blk, double* const* cols);
@@ -290,12 +288,13 @@ static int minres_block_impl(hipeig_ctx* c, hipeig_csr* A, double sigma, double 
 
   const int bv = hipeig_block_pick_variant(c, A, K, 1);
   if (bv < 0) return 1;
-  const BcooView tview = hipeig_bcoo_view(A, K);
+  const BlockedLayout& L = A->b[layout_slot(K)];
+  const BcooView tview = hipeig_bcoo_view(A, L);
   if (bv == 2)
     HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_block_ka_kernel<2, K>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)HIPEIG_BCOO_LDS_MAX));
-  const int gA = (bv == 2) ? hipeig_bcoo_grid(A, K) : hipeig_rowowner_grid(c, A);
-  const int nsweepA = (bv == 2) ? (tview.nunits + gA - 1) / gA : 1;
+  const SweepGrid sg = (bv == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
+  const int gA = sg.wgs, nsweepA = sg.launches;
   HIPEIG_REQUIRE((int64_t)nsweepA * gA <= HIPEIG_MAX_PARTIALS, "too many sweeps for the partial-sum buffer");
   // element-wise kernels: every workgroup sums the previous kernel's gE x K partials in its prologue, so FEWER, fatter
   // workgroups pay twice (less prologue traffic, fewer partials).  Measured (tools/experiments/mrb_grid_sweep.sh, N = 1e6,
@@ -333,9 +332,9 @@ static int minres_block_impl(hipeig_ctx* c, hipeig_csr* A, double sigma, double 
       BcooView tv = tview;
       for (int sw = 0; sw < nsweepA; ++sw) {
         tv.unit_begin = sw * gA;
-        if (late) hipLaunchKernelGGL((minres_block_ka_kernel<2, K, 1>), dim3(gA), dim3(BCOO_THREADS), hipeig_bcoo_lds_bytes(A, K), c->stream,
+        if (late) hipLaunchKernelGGL((minres_block_ka_kernel<2, K, 1>), dim3(gA), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream,
                                      tv, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)sw * gA * K);
-        else hipLaunchKernelGGL((minres_block_ka_kernel<2, K>), dim3(gA), dim3(BCOO_THREADS), hipeig_bcoo_lds_bytes(A, K), c->stream,
+        else hipLaunchKernelGGL((minres_block_ka_kernel<2, K>), dim3(gA), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream,
                                 tv, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)sw * gA * K);
       }
     } else if (late) {

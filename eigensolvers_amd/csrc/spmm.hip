@@ -7,8 +7,6 @@
 struct PtrTable8 { const double* p[BCOO_KPACK]; };
 struct OutTable8 { double* p[BCOO_KPACK]; };
 
-static inline int layout_slot(int K) { return K == 4 ? 0 : K == 8 ? 1 : 2; }
-
 // ---- interleave / de-interleave ---------------------------------------------------------
 // Thread t owns the 16-byte pair (2t, 2t+1) of the block: row t / (K/2), operands 2(t % (K/2)) and the next,
 // so the block side is one fully coalesced 16-byte access per lane and every column is touched in
@@ -85,41 +83,8 @@ int hipeig_block_unpack(hipeig_ctx* c, int K, int64_t n, int k, const double* bl
   return 0;
 }
 
-// ---- TCOO-B construction -------------------------------------------------------------------
-// One cursor per (unit, window) tile: count, exclusive scan on the host, scatter.  The slot a
-// non-zero takes inside its tile depends on scheduling; the set of non-zeros of a tile does not
-// (the sweep adds with atomics, so no order inside a tile is promised anyway).
-__global__ void __launch_bounds__(256)
-bcoo_bin_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const double* __restrict__ val,
-                int64_t nrows, int rw, int wbits, int nwin, uint32_t* __restrict__ cursor,
-                uint32_t* __restrict__ b_idx, double* __restrict__ b_val, int fill) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const uint32_t wmask = (1u << wbits) - 1u;
-  for (int64_t r = wave; r < nrows; r += nwaves) {
-    const int64_t unit = r / rw;
-    const uint32_t rl = (uint32_t)(r - unit * rw);
-    uint32_t* cur = cursor + unit * nwin;
-    const int s = rowptr[r], e = rowptr[r + 1];
-    for (int p = s + lane; p < e; p += 64) {
-      const uint32_t cc = (uint32_t)col[p];
-      const uint32_t slot = atomicAdd(cur + (cc >> wbits), 1u);
-      if (fill) {
-        b_idx[slot] = (rl << wbits) | (cc & wmask);
-        b_val[slot] = val[p];
-      }
-    }
-  }
-}
-
-size_t hipeig_bcoo_lds_bytes(const hipeig_csr* A, int K) {
-  const auto& L = A->bl[layout_slot(K)];
-  return (size_t)L.rw * K * sizeof(double) + ((size_t)L.nwin + 2) * sizeof(uint32_t);
-}
-
-BcooView hipeig_bcoo_view(const hipeig_csr* A, int K) {
-  const auto& L = A->bl[layout_slot(K)];
+// ---- TCOO-B ---------------------------------------------------------------------------------
+BcooView hipeig_bcoo_view(const hipeig_csr* A, const BlockedLayout& L) {
   BcooView t;
   t.idx = L.idx; t.val = L.val; t.off = L.off;
   t.nunits = L.nunits; t.nwin = L.nwin; t.wbits = L.wbits; t.rw = L.rw;
@@ -128,25 +93,20 @@ BcooView hipeig_bcoo_view(const hipeig_csr* A, int K) {
   return t;
 }
 
-int hipeig_bcoo_grid(const hipeig_csr* A, int K) {
-  const auto& L = A->bl[layout_slot(K)];
-  return L.wgs_per_sweep < L.nunits ? L.wgs_per_sweep : L.nunits;
-}
-
 // Decide between the window-blocked and the row-owner block kernel for interleave width K and build the
 // former's layout (idempotent).  Returns 2 (TCOO-B) or 1 (row-owner), -1 on failure.  for_solve: the caller is the block
 // MINRES, whose sweeps leave per-workgroup partials - it cannot take a layout that needs more than HIPEIG_MAX_PARTIALS
 // workgroups per product and keeps the row-owner kernel there (N = 1e7: 16 sweeps of 256).
 int hipeig_block_pick_variant(hipeig_ctx* c, hipeig_csr* A, int K, int for_solve) {
-  auto& L = A->bl[layout_slot(K)];
+  BlockedLayout& L = A->b[layout_slot(K)];
   A->last_block_k = K;
   if (A->block_variant == 1 || A->nnz == 0 || A->nrows == 0) return A->last_block_variant = 1;
   // an operator pinned to a reproducible kernel (variants 1-3, 5) keeps that promise for block products and block
   // solves too: the row-owner kernel adds a row's terms in a fixed order, the window-blocked one uses fp64 atomics
   if (A->block_variant == 0 && (A->reproducible || (A->variant != 0 && A->variant != 4))) return A->last_block_variant = 1;
-  auto fits_solve = [&](const hipeig_csr::BcooLayout& l) {
-    const int64_t g = l.wgs_per_sweep < l.nunits ? l.wgs_per_sweep : l.nunits;
-    return g > 0 && ((l.nunits + g - 1) / g) * g <= HIPEIG_MAX_PARTIALS;
+  auto fits_solve = [](const BlockedLayout& l) {
+    const SweepGrid g = blocked_grid(l);
+    return (int64_t)g.launches * g.wgs <= HIPEIG_MAX_PARTIALS;
   };
   if (L.state == 1) return A->last_block_variant = (for_solve && A->block_variant == 0 && !fits_solve(L)) ? 1 : 2;
   if (L.state == 2 && A->block_variant == 0) return A->last_block_variant = 1;
@@ -179,49 +139,17 @@ int hipeig_block_pick_variant(hipeig_ctx* c, hipeig_csr* A, int K, int for_solve
     L.state = 2;
     return A->last_block_variant = 1;
   }
-  if (for_solve && A->block_variant == 0) {            // would the layout fit the solve?  (same arithmetic as below)
-    const int64_t nu = (A->nrows + rw - 1) / rw, g = nu < c->num_cu ? nu : c->num_cu;
-    if (((nu + g - 1) / g) * g > HIPEIG_MAX_PARTIALS) return A->last_block_variant = 1;      // state stays undecided: a product may still build it
-  }
-  const int64_t nunits = (A->nrows + rw - 1) / rw;
-  const size_t ntile = (size_t)nunits * (size_t)nwin;
-  if (ntile >= ((size_t)1 << 30)) { L.state = 2; return A->last_block_variant = 1; }
-  uint32_t* d_cur = nullptr;
-  if (hipMalloc((void**)&d_cur, ntile * sizeof(uint32_t)) != hipSuccess) { hipeig_set_error("out of device memory (TCOO-B cursors)"); return -1; }
-  hipMemsetAsync(d_cur, 0, ntile * sizeof(uint32_t), c->stream);
-  const int grid = 8 * c->num_cu;
-  hipLaunchKernelGGL(bcoo_bin_kernel, dim3(grid), dim3(256), 0, c->stream, A->d_rowptr, A->d_col, A->d_val, A->nrows,
-                     (int)rw, wbits, (int)nwin, d_cur, (uint32_t*)nullptr, (double*)nullptr, 0);
-  std::vector<uint32_t> off(ntile + 1);
-  if (hipMemcpyAsync(off.data(), d_cur, ntile * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess) { hipFree(d_cur); hipeig_set_error("TCOO-B count pass failed"); return -1; }
-  uint64_t run = 0;
-  for (size_t i = 0; i < ntile; ++i) { const uint32_t n = off[i]; off[i] = (uint32_t)run; run += n; }
-  off[ntile] = (uint32_t)run;
-  if (run != (uint64_t)A->nnz) { hipFree(d_cur); hipeig_set_error("TCOO-B count pass lost non-zeros"); return -1; }
-  bool ok = hipMemcpyAsync(d_cur, off.data(), ntile * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess;
-  ok = ok && hipMalloc((void**)&L.off, (ntile + 1) * sizeof(uint32_t)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&L.idx, (size_t)A->nnz * sizeof(uint32_t)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&L.val, (size_t)A->nnz * sizeof(double)) == hipSuccess;
-  ok = ok && hipMemcpyAsync(L.off, off.data(), (ntile + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(bcoo_bin_kernel, dim3(grid), dim3(256), 0, c->stream, A->d_rowptr, A->d_col, A->d_val, A->nrows,
-                       (int)rw, wbits, (int)nwin, d_cur, L.idx, L.val, 1);
-    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;   // `off` must outlive the copies
-  }
-  hipFree(d_cur);
-  if (!ok) {
-    if (L.off) hipFree(L.off);
-    if (L.idx) hipFree(L.idx);
-    if (L.val) hipFree(L.val);
-    L.off = nullptr; L.idx = nullptr; L.val = nullptr;
-    hipeig_set_error("TCOO-B build failed (out of device memory?)");
-    return -1;
-  }
-  L.nunits = (int)nunits; L.nwin = (int)nwin; L.wbits = wbits; L.rw = (int)rw;
-  L.wgs_per_sweep = c->num_cu;                          // one 1024-thread workgroup (all of the LDS) per CU
+  BlockedLayout G{};
+  G.nunits = (int)((A->nrows + rw - 1) / rw); G.nwin = (int)nwin; G.wbits = wbits; G.rw = (int)rw;
+  G.binbits = wbits;                                     // one bin per window
+  G.wgs_per_sweep = c->num_cu;                           // one 1024-thread workgroup (all of the LDS) per CU
+  G.csplit = 1;
+  // would the layout fit the solve?  state stays undecided: a product may still build it
+  if (for_solve && A->block_variant == 0 && !fits_solve(G)) return A->last_block_variant = 1;
+  const int rc = hipeig_build_binned(c, A, G, 0, &L);
+  if (rc == 2) { L.state = 2; return A->last_block_variant = 1; }
+  if (rc) return -1;
   L.state = 1;
-  A->bytes += (int64_t)A->nnz * 12 + (int64_t)(ntile + 1) * 4;
   return A->last_block_variant = 2;
 }
 
@@ -291,11 +219,12 @@ static int spmm_block_run(hipeig_ctx* c, hipeig_csr* A, const double* Xb, const 
   if (hipeig_block_allgather(c, A, K, Xb, &xg)) return 4;
   if (bv == 2) {
     HIPEIG_CHECK(hipFuncSetAttribute((const void*)spmm_bcoo_kernel<K, Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_BCOO_LDS_MAX));
-    BcooView t = hipeig_bcoo_view(A, K);
-    const int g = hipeig_bcoo_grid(A, K);
-    for (int ub = 0; ub < t.nunits; ub += g) {                // one launch per sweep of the windows
-      t.unit_begin = ub;
-      hipLaunchKernelGGL((spmm_bcoo_kernel<K, Epi>), dim3(g), dim3(BCOO_THREADS), hipeig_bcoo_lds_bytes(A, K), c->stream, t, xg, epi);
+    const BlockedLayout& L = A->b[layout_slot(K)];
+    BcooView t = hipeig_bcoo_view(A, L);
+    const SweepGrid g = blocked_grid(L);
+    for (int i = 0; i < g.launches; ++i) {                    // one launch per sweep of the windows
+      t.unit_begin = i * g.wgs;
+      hipLaunchKernelGGL((spmm_bcoo_kernel<K, Epi>), dim3(g.wgs), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream, t, xg, epi);
     }
   } else {
     hipLaunchKernelGGL((spmm_rowowner_kernel<K, Epi>), dim3(hipeig_rowowner_grid(c, A)), dim3(HIPEIG_BLOCK), 0, c->stream,
@@ -398,7 +327,7 @@ extern "C" int hipeig_spmm_shift_pairs(hipeig_ctx* c, hipeig_csr* A, int npairs,
 }
 
 extern "C" int hipeig_csr_block_info(hipeig_csr* A, int64_t info[4]) {
-  const auto& L = A->bl[layout_slot(A->last_block_k == 4 ? 4 : A->last_block_k == 16 ? 16 : 8)];
+  const BlockedLayout& L = A->b[layout_slot(A->last_block_k == 4 ? 4 : A->last_block_k == 16 ? 16 : 8)];
   info[0] = A->last_block_variant; info[1] = L.nunits; info[2] = L.nwin; info[3] = L.rw;
   return 0;
 }

@@ -5,7 +5,6 @@
 
 int hipeig_csr_pick_variant(hipeig_ctx* c, hipeig_csr* A);
 size_t hipeig_tcoo_lds_bytes(const hipeig_csr* A);
-size_t hipeig_tcoow_lds_bytes(const hipeig_csr* A);
 static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair);
 
 // y[r] = a_self*xl[r] + a_sum*sum  (a_self = 0, a_sum = 1: plain product;
@@ -131,28 +130,13 @@ spmv_tcoow_combine_kernel(const double* __restrict__ parts, int nparts, int64_t 
   tcoow_combine_sweep(parts, nparts, stride, nrows, epi, acc);
 }
 
-TcooView hipeig_tcoow_view(const hipeig_csr* A) {
+// Device view of a TCOO-family copy: TCOO (A->t), TCOO-W (A->w) or the pair copy of TCOO-W (A->p)
+TcooView hipeig_tcoo_view(const hipeig_csr* A, const BlockedLayout& L) {
   TcooView t;
-  t.idx = A->w_idx; t.val = A->w_val; t.off = A->w_off;
-  t.nunits = A->w_nunits; t.nwin = A->w_nwin; t.wbits = A->w_wbits; t.rw = A->w_rw;
+  t.idx = L.idx; t.val = L.val; t.off = L.off;
+  t.nunits = L.nunits; t.nwin = L.nwin; t.wbits = L.wbits; t.rw = L.rw;
   t.unit_begin = 0;
-  t.prefetch = 0;
-  t.ablate = 0;
-  if (const char* e = getenv("HIPEIG_TCOO_ABLATE")) t.ablate = atoi(e);   // timing experiments (wrong results)
-  t.nrows = A->nrows;
-  t.gather_len = A->gather_len;
-  t.nrun = 0; t.yinit = nullptr; t.raw_out = nullptr;
-  t.csplit = 1; t.part_base = 0; t.part_stride = 0;
-  t.fx_xmax = nullptr; t.fx_count = 0; t.fx_bound = 0.0;
-  return t;
-}
-
-TcooView hipeig_tcoo_view(const hipeig_csr* A) {
-  TcooView t;
-  t.idx = A->t_idx; t.val = A->t_val; t.off = A->t_off;
-  t.nunits = A->t_nunits; t.nwin = A->t_nwin; t.wbits = A->t_wbits; t.rw = A->t_rw;
-  t.unit_begin = 0;
-  t.prefetch = A->t_prefetch;
+  t.prefetch = (&L == &A->t) ? A->t_prefetch : 0;
   t.ablate = 0;
   if (const char* e = getenv("HIPEIG_TCOO_ABLATE")) t.ablate = atoi(e);   // timing experiments (wrong results)
   t.nrows = A->nrows;
@@ -175,25 +159,18 @@ CsrView hipeig_csr_view(const hipeig_csr* A) {
   return v;
 }
 
-int hipeig_spmv_grid(const hipeig_csr* A, int variant) {
-  int64_t g;
-  if (variant == 4) {
-    g = A->w_wgs_per_sweep;                          // one unit per workgroup, one workgroup per CU
-    if (g > A->w_nunits) g = A->w_nunits;
-    if (A->w_csplit > 1) g = (int64_t)A->w_nunits * A->w_csplit;      // split mode: always a single launch
-  } else if (variant == 3) {
-    g = A->t_wgs_per_sweep;                          // workgroups of ONE sweep (4 units each)
-    const int64_t need = (A->t_nunits + 3) / 4;
-    if (g > need) g = need;
-  } else if (variant == 1) {
+// Workgroups per launch and sweep launches of one product with `variant` (4 stands for 5 too)
+SweepGrid hipeig_sweep_grid(const hipeig_csr* A, int variant) {
+  if (variant == 4 || variant == 5) return blocked_grid(A->w);
+  if (variant == 3) return blocked_grid(A->t, 4);
+  int64_t g = A->n_row_blocks;
+  if (variant == 1) {
     const int64_t groups_per_block = HIPEIG_BLOCK / A->lanes_per_row;
     g = (A->nrows + groups_per_block - 1) / groups_per_block;
-  } else {
-    g = A->n_row_blocks;
   }
   if (g < 1) g = 1;
   if (g > HIPEIG_MAX_PARTIALS) g = HIPEIG_MAX_PARTIALS;
-  return (int)g;
+  return SweepGrid{(int)g, 1};
 }
 
 // Partial-sum slabs of the split / overlapped sweeps (context buffer, grown on demand).
@@ -227,7 +204,7 @@ struct WindowSets {
 
 static void tcoow_window_sets(const hipeig_ctx* c, const hipeig_csr* A, WindowSets* ws) {
   const GatherLayout& gl = A->gl;
-  const int wb = A->w_wbits, nwin = A->w_nwin;
+  const int wb = A->w.wbits, nwin = A->w.nwin;
   const int64_t W = (int64_t)1 << wb;
   memset(ws, 0, sizeof(*ws));
   ws->nset = 1 + gl.nchunks;
@@ -264,10 +241,10 @@ static void tcoow_window_sets(const hipeig_ctx* c, const hipeig_csr* A, WindowSe
 // Allocate the slabs one product of A can need, so that no allocation happens later (a hipGraph
 // capture must not allocate).
 int hipeig_tcoow_reserve(hipeig_ctx* c, const hipeig_csr* A) {
-  if (!A->w_idx) return 0;
+  if (!A->w.idx) return 0;
   const int64_t stride = hipeig_tcoow_part_stride(A);
   const int nl = c->collectives ? 1 + A->gl.nchunks : 1;
-  const int64_t need = (A->w_csplit > 1) ? (int64_t)nl * A->w_csplit * stride : (c->collectives ? A->nrows : 0);
+  const int64_t need = (A->w.csplit > 1) ? (int64_t)nl * A->w.csplit * stride : (c->collectives ? A->nrows : 0);
   return need > 0 ? tcoow_ensure_parts(c, need) : 0;
 }
 
@@ -290,11 +267,11 @@ struct TcoowPlan {
 };
 
 int hipeig_tcoow_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, TcoowPlan* P) {
-  const int cs = A->w_csplit;
+  const int cs = A->w.csplit;
   const int64_t stride = hipeig_tcoow_part_stride(A);
   P->nlaunch = 0; P->ncombine = 0; P->xg = nullptr; P->overlapped = false;
   WindowSets ws;
-  bool split_sets = c->collectives && c->overlap && A->w_idx && A->col_stride > 0 && A->last_variant != 5;   // the fixed-point form needs max|x| of the whole operand first
+  bool split_sets = c->collectives && c->overlap && A->w.idx && A->col_stride > 0 && A->last_variant != 5;   // the fixed-point form needs max|x| of the whole operand first
   if (split_sets) {
     tcoow_window_sets(c, A, &ws);
     int nonempty = 0;
@@ -304,7 +281,7 @@ int hipeig_tcoow_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, Tcoow
   }
   if (!split_sets) {
     if (hipeig_allgather_x(c, A->gl, x_local, A->nrows, &P->xg)) return 4;
-    TcooView t = hipeig_tcoow_view(A);
+    TcooView t = hipeig_tcoo_view(A, A->w);
     if (cs > 1) {
       if (tcoow_ensure_parts(c, cs * stride)) return 4;
       t.csplit = cs; t.part_base = 0; t.part_stride = stride; t.raw_out = c->ytmp;
@@ -321,7 +298,7 @@ int hipeig_tcoow_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, Tcoow
   int li = 0;
   for (int q = 0; q < ws.nset; ++q) {
     if (ws.nrun[q] == 0) continue;
-    TcooView t = hipeig_tcoow_view(A);
+    TcooView t = hipeig_tcoo_view(A, A->w);
     t.nrun = ws.nrun[q];
     for (int r = 0; r < ws.nrun[q]; ++r) { t.run_lo[r] = ws.lo[q][r]; t.run_hi[r] = ws.hi[q][r]; }
     t.csplit = cs; t.part_stride = stride;
@@ -344,13 +321,14 @@ int hipeig_tcoow_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, Tcoow
   return 0;
 }
 
-// Raw (epilogue-free) launch of plan entry i, all its sweeps.
-static void tcoow_launch_raw(hipeig_ctx* c, hipeig_csr* A, TcooView t, const double* xg, int g, int fixed) {
-  AxpyEpilogue none{0.0, 0.0, nullptr, nullptr};
-  for (int ub = 0; ub < A->w_nunits * t.csplit; ub += g) {
-    t.unit_begin = ub;
-    if (fixed) hipLaunchKernelGGL(spmv_tcoow_kernel<1>, dim3(g), dim3(TCOOW_THREADS), hipeig_tcoow_lds_bytes(A), c->stream, t, xg, none);
-    else hipLaunchKernelGGL(spmv_tcoow_kernel<0>, dim3(g), dim3(TCOOW_THREADS), hipeig_tcoow_lds_bytes(A), c->stream, t, xg, none);
+// Every sweep launch of TCOO-W view t with epilogue `epi` (a plan entry's raw launch: the empty epilogue).
+static void tcoow_launch(hipeig_ctx* c, const hipeig_csr* A, TcooView t, const double* xg, int fixed, const AxpyEpilogue& epi) {
+  const SweepGrid g = blocked_grid(A->w);
+  const size_t lds = blocked_lds_bytes(A->w, 1);
+  for (int i = 0; i < g.launches; ++i) {
+    t.unit_begin = i * g.wgs;
+    if (fixed) hipLaunchKernelGGL(spmv_tcoow_kernel<1>, dim3(g.wgs), dim3(TCOOW_THREADS), lds, c->stream, t, xg, epi);
+    else hipLaunchKernelGGL(spmv_tcoow_kernel<0>, dim3(g.wgs), dim3(TCOOW_THREADS), lds, c->stream, t, xg, epi);
   }
 }
 
@@ -360,7 +338,6 @@ int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, i
                           const double** xg, int* ncombine) {
   TcoowPlan P;
   if (hipeig_tcoow_plan(c, A, x_local, &P)) return 4;
-  const int g = hipeig_spmv_grid(A, 4);
   const double* x = P.overlapped ? hipeig_gathered(c) : P.xg;
   const int nraw = P.ncombine ? P.nlaunch : P.nlaunch - 1;
   if (fixed) {                                              // never overlapped (hipeig_tcoow_plan): max|x| of the whole operand first
@@ -374,7 +351,7 @@ int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, i
       if (P.overlapped && !marked) { hipeig_phase_mark(c, 2); marked = true; }
     }
     if (i < nraw) {
-      tcoow_launch_raw(c, A, P.tv[i], x, g, fixed);
+      tcoow_launch(c, A, P.tv[i], x, fixed, AxpyEpilogue{0.0, 0.0, nullptr, nullptr});
       if (P.overlapped && i == 0) hipeig_phase_mark(c, 1);
     }
   }
@@ -397,19 +374,12 @@ static int launch_spmv(hipeig_ctx* c, hipeig_csr* A, double a_self, double a_sum
   const double* xg = nullptr;
   const bool fixed = (variant == 5);                 // TCOO-W with fixed-point accumulators
   if (fixed) variant = 4;
-  const int g = hipeig_spmv_grid(A, variant);
   if (variant == 4) {
     TcooView t;
     bool has_last = true;
     int ncombine = 0;
     if (hipeig_tcoow_run_plan(c, A, x, fixed ? 1 : 0, &t, &has_last, &xg, &ncombine)) return 4;
-    if (has_last) {
-      for (int ub = 0; ub < A->w_nunits * t.csplit; ub += g) {           // one launch per sweep
-        t.unit_begin = ub;
-        if (fixed) hipLaunchKernelGGL(spmv_tcoow_kernel<1>, dim3(g), dim3(TCOOW_THREADS), hipeig_tcoow_lds_bytes(A), c->stream, t, xg, epi);
-        else hipLaunchKernelGGL(spmv_tcoow_kernel<0>, dim3(g), dim3(TCOOW_THREADS), hipeig_tcoow_lds_bytes(A), c->stream, t, xg, epi);
-      }
-    }
+    if (has_last) tcoow_launch(c, A, t, xg, fixed ? 1 : 0, epi);      // one launch per sweep
     if (ncombine)
       hipLaunchKernelGGL(spmv_tcoow_combine_kernel, dim3(grid_for(A->nrows, 2)), dim3(HIPEIG_BLOCK), 0, c->stream,
                          c->ytmp, ncombine, t.part_stride, A->nrows, epi);
@@ -419,16 +389,17 @@ static int launch_spmv(hipeig_ctx* c, hipeig_csr* A, double a_self, double a_sum
   }
   if (hipeig_allgather_x(c, A->gl, x, A->nrows, &xg)) return 4;
   const CsrView v = hipeig_csr_view(A);
+  const SweepGrid g = hipeig_sweep_grid(A, variant);
   if (variant == 3) {
-    TcooView t = hipeig_tcoo_view(A);
-    for (int ub = 0; ub < A->t_nunits; ub += g * 4) {            // one launch per sweep
-      t.unit_begin = ub;
-      hipLaunchKernelGGL(spmv_tcoo_kernel, dim3(g), dim3(HIPEIG_BLOCK), hipeig_tcoo_lds_bytes(A), c->stream, t, xg, epi);
+    TcooView t = hipeig_tcoo_view(A, A->t);
+    for (int i = 0; i < g.launches; ++i) {                       // one launch per sweep, 4 units per workgroup
+      t.unit_begin = i * g.wgs * 4;
+      hipLaunchKernelGGL(spmv_tcoo_kernel, dim3(g.wgs), dim3(HIPEIG_BLOCK), hipeig_tcoo_lds_bytes(A), c->stream, t, xg, epi);
     }
   } else if (variant == 1)
-    hipLaunchKernelGGL(spmv_vector_kernel, dim3(g), dim3(HIPEIG_BLOCK), 0, c->stream, v, xg, epi);
+    hipLaunchKernelGGL(spmv_vector_kernel, dim3(g.wgs), dim3(HIPEIG_BLOCK), 0, c->stream, v, xg, epi);
   else
-    hipLaunchKernelGGL(spmv_stream_kernel, dim3(g), dim3(HIPEIG_BLOCK), 0, c->stream, v, xg, epi);
+    hipLaunchKernelGGL(spmv_stream_kernel, dim3(g.wgs), dim3(HIPEIG_BLOCK), 0, c->stream, v, xg, epi);
   HIPEIG_CHECK(hipGetLastError());
   hipeig_phase_mark(c, 3);
   return 0;
@@ -458,16 +429,12 @@ static int launch_spmv_pair(hipeig_ctx* c, hipeig_csr* A, double zr, double zi, 
       double* xp = c->ytmp;
       hipLaunchKernelGGL(pair_pack_kernel, dim3(grid_stream(2 * A->gather_len)), dim3(HIPEIG_BLOCK), 0, c->stream,
                          A->gather_len, xr, xi, reinterpret_cast<double2*>(xp));
-      TcooView t = hipeig_tcoow_view(A);
-      t.idx = A->p_idx; t.val = A->p_val; t.off = A->p_off;
-      t.nunits = A->p_nunits; t.nwin = A->p_nwin; t.wbits = A->p_wbits; t.rw = A->p_rw;
-      t.nrun = 0;
+      TcooView t = hipeig_tcoo_view(A, A->p);
       PairEpilogue epi{ar, ai, as, xr + A->row_offset, xi + A->row_offset, yr, yi};
-      int g = A->p_wgs_per_sweep < A->p_nunits ? A->p_wgs_per_sweep : A->p_nunits;
-      const size_t lds = (size_t)2 * A->p_rw * sizeof(double) + ((size_t)A->p_nwin + 2) * sizeof(uint32_t);
-      for (int ub = 0; ub < A->p_nunits; ub += g) {                    // one launch per sweep
-        t.unit_begin = ub;
-        hipLaunchKernelGGL(spmv_tcoow_pair_kernel, dim3(g), dim3(TCOOW_THREADS), lds, c->stream, t, xp, epi);
+      const SweepGrid g = blocked_grid(A->p);
+      for (int i = 0; i < g.launches; ++i) {                            // one launch per sweep
+        t.unit_begin = i * g.wgs;
+        hipLaunchKernelGGL(spmv_tcoow_pair_kernel, dim3(g.wgs), dim3(TCOOW_THREADS), blocked_lds_bytes(A->p, 2), c->stream, t, xp, epi);
       }
       HIPEIG_CHECK(hipGetLastError());
       A->last_pair_fused = 1;
@@ -495,10 +462,7 @@ extern "C" int hipeig_spmv_shift_pair(hipeig_ctx* c, hipeig_csr* A, double zr, d
 extern "C" int hipeig_csr_pair_info(hipeig_csr* A, int64_t out[2]) {
   out[0] = A->last_pair_fused;
   out[1] = 0;
-  if (A->last_pair_fused && A->p_nunits > 0) {
-    const int g = A->p_wgs_per_sweep < A->p_nunits ? A->p_wgs_per_sweep : A->p_nunits;
-    out[1] = (A->p_nunits + g - 1) / g;
-  }
+  if (A->last_pair_fused && A->p.nunits > 0) out[1] = blocked_grid(A->p).launches;
   return 0;
 }
 
@@ -524,8 +488,8 @@ __global__ void __launch_bounds__(256)
 tcoo_build_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                   const double* __restrict__ val, int64_t nrows, int rw, int nwin, int wbits,
                   uint32_t* __restrict__ counts /* [nunits][nwin], count pass */,
-                  const uint32_t* __restrict__ off /* fill pass */, uint32_t* __restrict__ t_idx,
-                  double* __restrict__ t_val, int fill) {
+                  const uint32_t* __restrict__ off /* fill pass */, uint32_t* __restrict__ idx_out,
+                  double* __restrict__ val_out, int fill) {
   extern __shared__ uint32_t tb_lds[];               // cnt[256][nwin] then base[nwin]
   uint32_t* cnt = tb_lds;
   uint32_t* base = tb_lds + 256 * nwin;
@@ -559,8 +523,8 @@ tcoo_build_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
         const int cc = col[p];
         const int c = cc >> wbits;
         const uint32_t dst = cnt[t * nwin + c]++;
-        t_idx[dst] = (rl << wbits) | ((uint32_t)cc & ((1u << wbits) - 1u));
-        t_val[dst] = val[p];
+        idx_out[dst] = (rl << wbits) | ((uint32_t)cc & ((1u << wbits) - 1u));
+        val_out[dst] = val[p];
       }
     }
     __syncthreads();
@@ -569,12 +533,12 @@ tcoo_build_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
     for (int c = t; c < nwin; c += 256) counts[(size_t)u * nwin + c] = base[c];
 }
 
-size_t hipeig_tcoo_lds_bytes(const hipeig_csr* A) { return (size_t)4 * A->t_rw * sizeof(double); }
+size_t hipeig_tcoo_lds_bytes(const hipeig_csr* A) { return (size_t)4 * A->t.rw * sizeof(double); }
 
 // Build the column-window blocked copy (idempotent).  Returns 0 on success, 1 on failure,
 // 2 if the operator does not suit the layout (caller falls back to the CSR-stream kernel).
 int hipeig_csr_build_tcoo(hipeig_ctx* c, hipeig_csr* A) {
-  if (A->t_idx) return 0;
+  if (A->t.idx) return 0;
   if (A->nnz == 0 || A->nrows == 0) return 2;
   int wbits = TCOO_MAX_WBITS;
   if (const char* e = getenv("HIPEIG_TCOO_WBITS")) wbits = atoi(e);          // tuning knob
@@ -590,58 +554,63 @@ int hipeig_csr_build_tcoo(hipeig_ctx* c, hipeig_csr* A) {
   if (const char* e = getenv("HIPEIG_TCOO_RW")) rw = (atoi(e) + 63) / 64 * 64;   // tuning knob
   HIPEIG_REQUIRE(rw >= 64 && rw * 32 <= 163840, "HIPEIG_TCOO_RW out of range");
   if (rw > ((int64_t)1 << (32 - wbits))) rw = (int64_t)1 << (32 - wbits);
-  const int nunits = (int)((A->nrows + rw - 1) / rw);
-  uint32_t* d_counts = nullptr;
-  const size_t ntile = (size_t)nunits * nwin;
-  HIPEIG_CHECK(hipMalloc((void**)&d_counts, ntile * sizeof(uint32_t)));
+  int per_cu = (int)(163840 / ((size_t)4 * rw * sizeof(double)));             // LDS-limited residency
+  if (per_cu > 8) per_cu = 8;
+  if (per_cu < 1) per_cu = 1;
+  if (const char* e = getenv("HIPEIG_TCOO_WG_PER_CU")) per_cu = atoi(e);      // tuning knob
+  HIPEIG_REQUIRE(per_cu >= 1 && per_cu <= 8, "HIPEIG_TCOO_WG_PER_CU out of range");
+  BlockedLayout L{};
+  L.nunits = (int)((A->nrows + rw - 1) / rw); L.nwin = nwin; L.wbits = wbits; L.rw = (int)rw;
+  L.wgs_per_sweep = per_cu * c->num_cu; L.csplit = 1; L.slots = A->nnz;
+  const size_t ntile = (size_t)L.nunits * nwin;
   const size_t lds = ((size_t)256 * nwin + nwin) * sizeof(uint32_t);
-  HIPEIG_CHECK(hipFuncSetAttribute((const void*)tcoo_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(((size_t)256 * TCOO_MAX_WIN + TCOO_MAX_WIN) * sizeof(uint32_t))));
-  hipLaunchKernelGGL(tcoo_build_kernel, dim3(nunits), dim3(256), lds, c->stream, A->d_rowptr, A->d_col, A->d_val,
-                     A->nrows, (int)rw, nwin, wbits, d_counts, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                     (double*)nullptr, 0);
-  HIPEIG_CHECK(hipGetLastError());
-  std::vector<uint32_t> off(ntile + 1);
-  HIPEIG_CHECK(hipMemcpyAsync(off.data() + 1, d_counts, ntile * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPEIG_CHECK(hipStreamSynchronize(c->stream));
-  off[0] = 0;
-  uint64_t run = 0;
-  for (size_t i = 1; i <= ntile; ++i) { run += off[i]; off[i] = (uint32_t)run; }
-  HIPEIG_REQUIRE(run == (uint64_t)A->nnz, "TCOO count pass lost non-zeros");
-  HIPEIG_CHECK(hipFree(d_counts));
-  HIPEIG_CHECK(hipMalloc((void**)&A->t_off, (ntile + 1) * sizeof(uint32_t)));
-  HIPEIG_CHECK(hipMalloc((void**)&A->t_idx, (size_t)A->nnz * sizeof(uint32_t)));
-  HIPEIG_CHECK(hipMalloc((void**)&A->t_val, (size_t)A->nnz * sizeof(double)));
-  HIPEIG_CHECK(hipMemcpyAsync(A->t_off, off.data(), (ntile + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(tcoo_build_kernel, dim3(nunits), dim3(256), lds, c->stream, A->d_rowptr, A->d_col, A->d_val,
-                     A->nrows, (int)rw, nwin, wbits, (uint32_t*)nullptr, (const uint32_t*)A->t_off, A->t_idx, A->t_val, 1);
-  HIPEIG_CHECK(hipGetLastError());
-  HIPEIG_CHECK(hipStreamSynchronize(c->stream));
-  A->t_nunits = nunits; A->t_nwin = nwin; A->t_wbits = wbits; A->t_rw = (int)rw;
-  {
-    int per_cu = (int)(163840 / ((size_t)4 * rw * sizeof(double)));           // LDS-limited residency
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    if (const char* e = getenv("HIPEIG_TCOO_WG_PER_CU")) per_cu = atoi(e);    // tuning knob
-    HIPEIG_REQUIRE(per_cu >= 1 && per_cu <= 8, "HIPEIG_TCOO_WG_PER_CU out of range");
-    A->t_wgs_per_sweep = per_cu * c->num_cu;
-    A->t_prefetch = 0;
-    if (const char* e = getenv("HIPEIG_TCOO_PREFETCH")) A->t_prefetch = atoi(e) != 0;   // tuning knob
-  }
-  HIPEIG_CHECK(hipFuncSetAttribute((const void*)spmv_tcoo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)HIPEIG_TCOO_LDS_MAX));   // the largest any operator may ask for
+  uint32_t* d_counts = nullptr;
+  auto build = [&]() -> int {
+    HIPEIG_CHECK(hipMalloc((void**)&d_counts, ntile * sizeof(uint32_t)));
+    HIPEIG_CHECK(hipFuncSetAttribute((const void*)tcoo_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(((size_t)256 * TCOO_MAX_WIN + TCOO_MAX_WIN) * sizeof(uint32_t))));
+    hipLaunchKernelGGL(tcoo_build_kernel, dim3(L.nunits), dim3(256), lds, c->stream, A->d_rowptr, A->d_col, A->d_val,
+                       A->nrows, L.rw, nwin, wbits, d_counts, (const uint32_t*)nullptr, (uint32_t*)nullptr, (double*)nullptr, 0);
+    HIPEIG_CHECK(hipGetLastError());
+    std::vector<uint32_t> off(ntile + 1);
+    HIPEIG_CHECK(hipMemcpyAsync(off.data() + 1, d_counts, ntile * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPEIG_CHECK(hipStreamSynchronize(c->stream));
+    off[0] = 0;
+    uint64_t run = 0;
+    for (size_t i = 1; i <= ntile; ++i) { run += off[i]; off[i] = (uint32_t)run; }
+    HIPEIG_REQUIRE(run == (uint64_t)A->nnz, "TCOO count pass lost non-zeros");
+    HIPEIG_CHECK(hipMalloc((void**)&L.off, (ntile + 1) * sizeof(uint32_t)));
+    HIPEIG_CHECK(hipMalloc((void**)&L.idx, (size_t)A->nnz * sizeof(uint32_t)));
+    HIPEIG_CHECK(hipMalloc((void**)&L.val, (size_t)A->nnz * sizeof(double)));
+    HIPEIG_CHECK(hipMemcpyAsync(L.off, off.data(), (ntile + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(tcoo_build_kernel, dim3(L.nunits), dim3(256), lds, c->stream, A->d_rowptr, A->d_col, A->d_val,
+                       A->nrows, L.rw, nwin, wbits, (uint32_t*)nullptr, (const uint32_t*)L.off, L.idx, L.val, 1);
+    HIPEIG_CHECK(hipGetLastError());
+    HIPEIG_CHECK(hipStreamSynchronize(c->stream));
+    HIPEIG_CHECK(hipFuncSetAttribute((const void*)spmv_tcoo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)HIPEIG_TCOO_LDS_MAX));   // the largest any operator may ask for
+    return 0;
+  };
+  const int rc = build();
+  if (d_counts) hipFree(d_counts);
+  if (rc) { hipeig_free_layout(&L); return rc; }
+  A->t = L;
+  A->t_prefetch = 0;
+  if (const char* e = getenv("HIPEIG_TCOO_PREFETCH")) A->t_prefetch = atoi(e) != 0;   // tuning knob
   A->bytes += (int64_t)A->nnz * 12 + (int64_t)(ntile + 1) * 4;
   return 0;
 }
 
-// ---- TCOO-W construction --------------------------------------------------------------------
+// ---- binned copies: TCOO-W, its pair copy, TCOO-B ----------------------------------------------
 // Bucketing by (unit, column bin) with global counters: count, scan on the host, scatter.
 // Which slot of its bin a non-zero lands in depends on scheduling; the SET of non-zeros of
-// every bin does not, and the kernel's accumulation order is unordered anyway.
+// every bin does not, and the sweeps' accumulation order is unordered anyway.
+// LANE_MAJOR: slots are stored lane-major inside their 256-slot batch (TCOO-W, tcoow_islot / tcoow_vslot).
+template <int LANE_MAJOR>
 __global__ void __launch_bounds__(256)
-tcoow_bin_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                 const double* __restrict__ val, int64_t nrows, int rw, int binbits, int nbins, int wbits,
-                 uint32_t* __restrict__ cursor, uint32_t* __restrict__ w_idx, double* __restrict__ w_val, int fill) {
+bin_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+           const double* __restrict__ val, int64_t nrows, int rw, int binbits, int nbins, int wbits,
+           uint32_t* __restrict__ cursor, uint32_t* __restrict__ idx_out, double* __restrict__ val_out, int fill) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -655,23 +624,105 @@ tcoow_bin_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__
       const uint32_t cc = (uint32_t)col[p];
       const uint32_t slot = atomicAdd(cur + (cc >> binbits), 1u);
       if (fill) {
-        w_idx[tcoow_islot(slot)] = (rl << wbits) | (cc & wmask);      // lane-major inside its 256-slot batch
-        w_val[tcoow_vslot(slot)] = val[p];
+        idx_out[LANE_MAJOR ? tcoow_islot(slot) : slot] = (rl << wbits) | (cc & wmask);
+        val_out[LANE_MAJOR ? tcoow_vslot(slot) : slot] = val[p];
       }
     }
   }
 }
 
-size_t hipeig_tcoow_lds_bytes(const hipeig_csr* A) {
-  return (size_t)A->w_rw * sizeof(double) + ((size_t)A->w_nwin + 2) * sizeof(uint32_t);
+void hipeig_free_layout(BlockedLayout* L) {
+  if (L->idx) hipFree(L->idx);
+  if (L->val) hipFree(L->val);
+  if (L->off) hipFree(L->off);
+  L->idx = nullptr; L->val = nullptr; L->off = nullptr;
 }
 
-// pair = 1 builds the copy of the pair sweep (two accumulators per row, so half the rows per unit; no column
-// splits) into the p_* fields; everything else is the same construction.
+int hipeig_build_binned(hipeig_ctx* c, hipeig_csr* A, const BlockedLayout& geom, unsigned policy, BlockedLayout* out) {
+  const int bpw = 1 << (geom.wbits - geom.binbits);    // bins per window
+  const int64_t nbins = (int64_t)geom.nwin * bpw;
+  const size_t ntile = (size_t)geom.nunits * geom.nwin, ncnt = (size_t)geom.nunits * nbins;
+  HIPEIG_REQUIRE(ncnt < ((size_t)1 << 30), "too many (unit, bin) counters");
+  BlockedLayout L = geom;
+  L.idx = nullptr; L.val = nullptr; L.off = nullptr;
+  L.align = (policy & BIN_GROUP_ALIGN) ? 1 : 0;
+  uint32_t* d_cur = nullptr;
+  auto scatter = [&](uint32_t* idx, double* val, int fill) {
+    const int grid = 8 * c->num_cu;
+    if (policy & BIN_LANE_MAJOR)
+      hipLaunchKernelGGL(bin_kernel<1>, dim3(grid), dim3(256), 0, c->stream, A->d_rowptr, A->d_col, A->d_val, A->nrows,
+                         L.rw, L.binbits, (int)nbins, L.wbits, d_cur, idx, val, fill);
+    else
+      hipLaunchKernelGGL(bin_kernel<0>, dim3(grid), dim3(256), 0, c->stream, A->d_rowptr, A->d_col, A->d_val, A->nrows,
+                         L.rw, L.binbits, (int)nbins, L.wbits, d_cur, idx, val, fill);
+  };
+  auto build = [&]() -> int {
+    HIPEIG_CHECK(hipMalloc((void**)&d_cur, ncnt * sizeof(uint32_t)));
+    HIPEIG_CHECK(hipMemsetAsync(d_cur, 0, ncnt * sizeof(uint32_t), c->stream));
+    scatter(nullptr, nullptr, 0);
+    HIPEIG_CHECK(hipGetLastError());
+    std::vector<uint32_t> cnt(ncnt);
+    HIPEIG_CHECK(hipMemcpyAsync(cnt.data(), d_cur, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPEIG_CHECK(hipStreamSynchronize(c->stream));
+    // Exclusive scan in place (-> scatter cursors) with the padding of `policy`: padding slots (index 0xFFFFFFFF,
+    // value 0) are skipped by the sweeps.
+    const bool unit_batch = policy & BIN_UNIT_BATCH, win_batch = policy & BIN_WIN_BATCH, align = L.align;
+    std::vector<uint32_t> off(ntile + 1);
+    uint64_t run = 0, counted = 0;
+    for (size_t i = 0; i < ncnt; ++i) {
+      if (i % bpw == 0) {
+        const size_t tile = i / bpw;
+        if ((unit_batch && tile % L.nwin == 0) || win_batch) run = (run + TCOOW_BATCH - 1) & ~(uint64_t)(TCOOW_BATCH - 1);
+        else if (align) run = (run + 63) & ~(uint64_t)63;
+        off[tile] = (uint32_t)run;
+      }
+      const uint32_t n = cnt[i];
+      if (align && n > 0 && n <= 64 && (run & 63) + n > 64) run = (run + 63) & ~(uint64_t)63;
+      cnt[i] = (uint32_t)run;
+      run += n;
+      counted += n;
+    }
+    off[ntile] = (uint32_t)run;
+    HIPEIG_REQUIRE(counted == (uint64_t)A->nnz, "count pass lost non-zeros");
+    if (unit_batch) run = (run + TCOOW_BATCH - 1) & ~(uint64_t)(TCOOW_BATCH - 1);     // the last batch is loaded whole
+    HIPEIG_REQUIRE(run < ((uint64_t)1 << 32), "blocked stream too long for 32-bit offsets");
+    L.slots = (int64_t)run;
+    const size_t nslots = (size_t)run;
+    HIPEIG_CHECK(hipMemcpyAsync(d_cur, cnt.data(), ncnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPEIG_CHECK(hipMalloc((void**)&L.off, (ntile + 1) * sizeof(uint32_t)));
+    if (policy & BIN_UNCACHED) {
+      HIPEIG_CHECK(hipExtMallocWithFlags((void**)&L.idx, nslots * sizeof(uint32_t), hipDeviceMallocUncached));
+      HIPEIG_CHECK(hipExtMallocWithFlags((void**)&L.val, nslots * sizeof(double), hipDeviceMallocUncached));
+    } else {
+      HIPEIG_CHECK(hipMalloc((void**)&L.idx, nslots * sizeof(uint32_t)));
+      HIPEIG_CHECK(hipMalloc((void**)&L.val, nslots * sizeof(double)));
+    }
+    if (nslots != (size_t)A->nnz) {
+      HIPEIG_CHECK(hipMemsetAsync(L.idx, 0xFF, nslots * sizeof(uint32_t), c->stream));
+      HIPEIG_CHECK(hipMemsetAsync(L.val, 0, nslots * sizeof(double), c->stream));
+    }
+    HIPEIG_CHECK(hipMemcpyAsync(L.off, off.data(), (ntile + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    scatter(L.idx, L.val, 1);
+    HIPEIG_CHECK(hipGetLastError());
+    HIPEIG_CHECK(hipStreamSynchronize(c->stream));     // `cnt` and `off` must outlive the copies
+    return 0;
+  };
+  const int rc = build();
+  if (d_cur) hipFree(d_cur);
+  if (rc) { hipeig_free_layout(&L); return rc; }
+  *out = L;
+  A->bytes += L.slots * 12 + (int64_t)(ntile + 1) * 4;
+  return 0;
+}
+
+// TCOO-W (pair = 0, into A->w) or the copy of the pair sweep (pair = 1, into A->p: two accumulators per row, so half
+// the rows per unit; no column splits).  Returns 0 on success, 1 on failure, 2 if the operator does not suit the layout.
 static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair) {
-  if (pair ? (A->p_idx != nullptr) : (A->w_idx != nullptr)) return 0;
+  BlockedLayout& out = pair ? A->p : A->w;
+  if (out.idx) return 0;
   if (A->nnz == 0 || A->nrows == 0) return 2;
-  const int64_t max_rw = pair ? TCOOW_MAX_RW / 2 : TCOOW_MAX_RW;
+  const int acc = pair ? 2 : 1;                        // accumulators per row
+  const int64_t max_rw = TCOOW_MAX_RW / acc;
   int wbits = 17;                                      // 15 bits are left for the row inside the unit
   if (const char* e = getenv(pair ? "HIPEIG_TCOOW_PAIR_WBITS" : "HIPEIG_TCOOW_WBITS")) wbits = atoi(e);         // tuning knob
   HIPEIG_REQUIRE(wbits >= 10 && wbits <= 17, "HIPEIG_TCOOW_WBITS out of range");
@@ -682,8 +733,6 @@ static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair) {
   if (const char* e = getenv(pair ? "HIPEIG_TCOOW_PAIR_BINBITS" : "HIPEIG_TCOOW_BINBITS")) binbits = atoi(e);     // tuning knob
   if (binbits > wbits) binbits = wbits;
   HIPEIG_REQUIRE(binbits >= 3, "HIPEIG_TCOOW_BINBITS out of range");
-  const int bpw = 1 << (wbits - binbits);
-  const int64_t nbins = (int64_t)nwin * bpw;
   // one unit per CU if it fits; otherwise the fewest sweeps that fit the LDS, with the rows spread
   // evenly over sweeps * CUs units so that the last sweep is as full as the first
   int64_t sweeps = (A->nrows + (int64_t)c->num_cu * max_rw - 1) / ((int64_t)c->num_cu * max_rw);
@@ -715,95 +764,36 @@ static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair) {
   }
   if (const char* e = getenv(pair ? "HIPEIG_TCOOW_PAIR_RW" : "HIPEIG_TCOOW_RW")) rw = (atoi(e) + 63) / 64 * 64;   // tuning knob
   HIPEIG_REQUIRE(rw >= 64 && rw <= max_rw && rw <= ((int64_t)1 << (32 - wbits)), "HIPEIG_TCOOW_RW out of range");
-  const int64_t nunits = (A->nrows + rw - 1) / rw;
-  const size_t ncnt = (size_t)(nunits * nbins);
-  HIPEIG_REQUIRE(ncnt < ((size_t)1 << 30), "too many (unit, bin) counters");
-  uint32_t* d_cur = nullptr;
-  HIPEIG_CHECK(hipMalloc((void**)&d_cur, ncnt * sizeof(uint32_t)));
-  HIPEIG_CHECK(hipMemsetAsync(d_cur, 0, ncnt * sizeof(uint32_t), c->stream));
-  const int grid = 8 * c->num_cu;
-  hipLaunchKernelGGL(tcoow_bin_kernel, dim3(grid), dim3(256), 0, c->stream, A->d_rowptr, A->d_col, A->d_val, A->nrows,
-                     (int)rw, binbits, (int)nbins, wbits, d_cur, (uint32_t*)nullptr, (double*)nullptr, 0);
-  HIPEIG_CHECK(hipGetLastError());
-  std::vector<uint32_t> cnt(ncnt);
-  HIPEIG_CHECK(hipMemcpyAsync(cnt.data(), d_cur, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPEIG_CHECK(hipStreamSynchronize(c->stream));
-  const size_t ntile = (size_t)nunits * nwin;
-  std::vector<uint32_t> off(ntile + 1);
+  BlockedLayout G{};
+  G.nunits = (int)((A->nrows + rw - 1) / rw); G.nwin = nwin; G.wbits = wbits; G.rw = (int)rw;
+  G.binbits = binbits; G.csplit = csplit;
+  int per_cu = (int)(163840 / (blocked_lds_bytes(G, acc) + 256));
+  if (per_cu > 2) per_cu = 2;                          // 1024-thread workgroups: at most 32 waves per CU
+  if (per_cu < 1) per_cu = 1;
+  if (const char* e = getenv("HIPEIG_TCOOW_WG_PER_LAUNCH_CU")) per_cu = atoi(e);   // tuning knob: workgroups per CU in ONE launch (2 with full-height units: both sweeps in one launch, the second workgroup of a CU starts when its first ends)
+  HIPEIG_REQUIRE(per_cu >= 1 && per_cu <= 8, "HIPEIG_TCOOW_WG_PER_LAUNCH_CU out of range");
+  G.wgs_per_sweep = per_cu * c->num_cu;
   // Bins never straddle a 64-element instruction group and tiles start on group boundaries (round 3; the gaps are
-  // padding slots - index 0xFFFFFFFF, value 0 - that the sweep skips; ~2 % of the stream).  A line of x is then fetched
-  // by exactly ONE gather instruction of one wave: L1 -> L2 read requests per launch 1.829e8 -> 1.704e8, i.e. gather fills
-  // per non-zero 0.468 -> 0.431 against the ideal (1 - exp(-k))/k = 0.426, and 2.083 -> 1.90 ms per product at N = 1e7
+  // padding slots that the sweep skips; ~2 % of the stream).  A line of x is then fetched by exactly ONE gather
+  // instruction of one wave: L1 -> L2 read requests per launch 1.829e8 -> 1.704e8, i.e. gather fills per non-zero
+  // 0.468 -> 0.431 against the ideal (1 - exp(-k))/k = 0.426, and 2.083 -> 1.90 ms per product at N = 1e7
   // (profiles/r03_spmv_aligned_bins.txt).  HIPEIG_TCOOW_ALIGN=0 restores the unaligned stream.
   // Whatever the knob, every stream range a wave can start on begins on a 256-slot batch (the sweep loads batches
   // lane-major, tcoow_islot / tcoow_vslot): unit starts, and on a row-partitioned operator every window start, since any window can
   // begin a run of the overlapped plan (hipeig_tcoow_plan).  Column-split shares are cut at batch multiples.
   const char* al_env = getenv(pair ? "HIPEIG_TCOOW_PAIR_ALIGN" : "HIPEIG_TCOOW_ALIGN");
-  const bool align = !(al_env && atoi(al_env) == 0);
-  const bool win_batches = A->col_stride > 0;
-  uint64_t run = 0, counted = 0;
-  for (size_t i = 0; i < ncnt; ++i) {
-    if (i % bpw == 0) {
-      const size_t tile = i / bpw;
-      if (tile % nwin == 0 || win_batches) run = (run + TCOOW_BATCH - 1) & ~(uint64_t)(TCOOW_BATCH - 1);
-      else if (align) run = (run + 63) & ~(uint64_t)63;
-      off[tile] = (uint32_t)run;
-    }
-    const uint32_t n = cnt[i];
-    if (align && n > 0 && n <= 64 && (run & 63) + n > 64) run = (run + 63) & ~(uint64_t)63;
-    cnt[i] = (uint32_t)run;                            // exclusive scan in place -> scatter cursors
-    run += n;
-    counted += n;
-  }
-  off[ntile] = (uint32_t)run;
-  HIPEIG_REQUIRE(counted == (uint64_t)A->nnz, "TCOO-W count pass lost non-zeros");
-  const uint64_t padded = (run + TCOOW_BATCH - 1) & ~(uint64_t)(TCOOW_BATCH - 1);     // the last batch is loaded whole
-  HIPEIG_REQUIRE(padded < ((uint64_t)1 << 32), "blocked stream too long for 32-bit offsets");
-  const size_t nslots = (size_t)padded;                // stream length incl. padding slots
-  HIPEIG_CHECK(hipMemcpyAsync(d_cur, cnt.data(), ncnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  uint32_t*& l_off = pair ? A->p_off : A->w_off;       // owned by the operator from the allocation on
-  uint32_t*& l_idx = pair ? A->p_idx : A->w_idx;
-  double*& l_val = pair ? A->p_val : A->w_val;
-  HIPEIG_CHECK(hipMalloc((void**)&l_off, (ntile + 1) * sizeof(uint32_t)));
-  {
-    // experiment knob: place the once-read stream in uncached (MTYPE_UC) memory so that it does not
-    // occupy L2 lines / tag bandwidth next to the x window
-    const char* uc = getenv("HIPEIG_TCOOW_UNCACHED");
-    if (uc && atoi(uc) != 0) {
-      HIPEIG_CHECK(hipExtMallocWithFlags((void**)&l_idx, nslots * sizeof(uint32_t), hipDeviceMallocUncached));
-      HIPEIG_CHECK(hipExtMallocWithFlags((void**)&l_val, nslots * sizeof(double), hipDeviceMallocUncached));
-    } else {
-      HIPEIG_CHECK(hipMalloc((void**)&l_idx, nslots * sizeof(uint32_t)));
-      HIPEIG_CHECK(hipMalloc((void**)&l_val, nslots * sizeof(double)));
-    }
-    if (nslots != (size_t)A->nnz) {                      // padding slots: sentinel index, zero value
-      HIPEIG_CHECK(hipMemsetAsync(l_idx, 0xFF, nslots * sizeof(uint32_t), c->stream));
-      HIPEIG_CHECK(hipMemsetAsync(l_val, 0, nslots * sizeof(double), c->stream));
-    }
-  }
-  HIPEIG_CHECK(hipMemcpyAsync(l_off, off.data(), (ntile + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(tcoow_bin_kernel, dim3(grid), dim3(256), 0, c->stream, A->d_rowptr, A->d_col, A->d_val, A->nrows,
-                     (int)rw, binbits, (int)nbins, wbits, d_cur, l_idx, l_val, 1);
-  HIPEIG_CHECK(hipGetLastError());
-  HIPEIG_CHECK(hipStreamSynchronize(c->stream));
-  HIPEIG_CHECK(hipFree(d_cur));
-  int per_cu = (int)(163840 / ((pair ? 2 : 1) * rw * sizeof(double) + ((size_t)nwin + 2) * sizeof(uint32_t) + 256));
-  if (per_cu > 2) per_cu = 2;                          // 1024-thread workgroups: at most 32 waves per CU
-  if (per_cu < 1) per_cu = 1;
-  if (const char* e = getenv("HIPEIG_TCOOW_WG_PER_LAUNCH_CU")) per_cu = atoi(e);   // tuning knob: workgroups per CU in ONE launch (2 with full-height units: both sweeps in one launch, the second workgroup of a CU starts when its first ends)
-  HIPEIG_REQUIRE(per_cu >= 1 && per_cu <= 8, "HIPEIG_TCOOW_WG_PER_LAUNCH_CU out of range");
+  // experiment knob: place the once-read stream in uncached (MTYPE_UC) memory so that it does not
+  // occupy L2 lines / tag bandwidth next to the x window
+  const char* uc = getenv("HIPEIG_TCOOW_UNCACHED");
+  const unsigned policy = BIN_LANE_MAJOR | BIN_UNIT_BATCH | (al_env && atoi(al_env) == 0 ? 0u : BIN_GROUP_ALIGN) |
+                          (A->col_stride > 0 ? BIN_WIN_BATCH : 0u) | (uc && atoi(uc) != 0 ? BIN_UNCACHED : 0u);
+  const int rc = hipeig_build_binned(c, A, G, policy, &out);
+  if (rc) return rc;
   if (pair) {
-    A->p_nunits = (int)nunits; A->p_nwin = nwin; A->p_wbits = wbits; A->p_rw = (int)rw;
-    A->p_wgs_per_sweep = per_cu * c->num_cu;
     HIPEIG_CHECK(hipFuncSetAttribute((const void*)spmv_tcoow_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)HIPEIG_TCOOW_LDS_MAX));
-    A->bytes += (int64_t)A->nnz * 12 + (int64_t)(ntile + 1) * 4;
     return 0;
   }
-  A->w_nunits = (int)nunits; A->w_nwin = nwin; A->w_wbits = wbits; A->w_rw = (int)rw;
-  A->w_csplit = csplit;
-  A->w_binbits = binbits; A->w_align = align ? 1 : 0; A->w_slots = (int64_t)nslots;
-  A->w_wgs_per_sweep = per_cu * c->num_cu;
   HIPEIG_CHECK(hipFuncSetAttribute((const void*)spmv_tcoow_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)HIPEIG_TCOOW_LDS_MAX));
   HIPEIG_CHECK(hipFuncSetAttribute((const void*)spmv_tcoow_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -820,7 +810,6 @@ static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair) {
     for (double v : part) m = (v > m || v != v) ? v : m;
     A->absrow_max = m;
   }
-  A->bytes += (int64_t)nslots * 12 + (int64_t)(ntile + 1) * 4;
   return 0;
 }
 
@@ -844,17 +833,7 @@ int hipeig_csr_pick_variant(hipeig_ctx* c, hipeig_csr* A) {
     if (rc == 2) variant = 2;
   }
   A->last_variant = variant;
-  A->last_launches = 1;
-  if (variant == 4 || variant == 5) {
-    int g = A->w_wgs_per_sweep < A->w_nunits ? A->w_wgs_per_sweep : A->w_nunits;
-    A->last_launches = (A->w_csplit > 1) ? 1 : (A->w_nunits + g - 1) / g;     // sweep launches (split mode adds a combine launch)
-  } else if (variant == 3) {
-    int64_t g = A->t_wgs_per_sweep;
-    const int64_t need = (A->t_nunits + 3) / 4;
-    if (g > need) g = need;
-    if (g > HIPEIG_MAX_PARTIALS) g = HIPEIG_MAX_PARTIALS;
-    A->last_launches = (int)((A->t_nunits + g * 4 - 1) / (g * 4));
-  }
+  A->last_launches = hipeig_sweep_grid(A, variant).launches;   // sweep launches (split mode adds a combine launch)
   return variant;
 }
 
@@ -972,20 +951,7 @@ extern "C" int hipeig_csr_destroy(hipeig_ctx* c, hipeig_csr* A) {
   if (A->d_col) hipFree(A->d_col);
   if (A->d_val) hipFree(A->d_val);
   if (A->d_row_blocks) hipFree(A->d_row_blocks);
-  if (A->t_idx) hipFree(A->t_idx);
-  if (A->t_val) hipFree(A->t_val);
-  if (A->t_off) hipFree(A->t_off);
-  if (A->w_idx) hipFree(A->w_idx);
-  if (A->w_val) hipFree(A->w_val);
-  if (A->w_off) hipFree(A->w_off);
-  if (A->p_idx) hipFree(A->p_idx);
-  if (A->p_val) hipFree(A->p_val);
-  if (A->p_off) hipFree(A->p_off);
-  for (int q = 0; q < 3; ++q) {
-    if (A->bl[q].idx) hipFree(A->bl[q].idx);
-    if (A->bl[q].val) hipFree(A->bl[q].val);
-    if (A->bl[q].off) hipFree(A->bl[q].off);
-  }
+  for (BlockedLayout* L : {&A->t, &A->w, &A->p, &A->b[0], &A->b[1], &A->b[2]}) hipeig_free_layout(L);
   free(A);
   return 0;
 }
@@ -998,15 +964,13 @@ extern "C" int hipeig_csr_destroy(hipeig_ctx* c, hipeig_csr* A) {
 extern "C" int hipeig_csr_layout_info(hipeig_csr* A, int64_t out[13]) {
   memset(out, 0, 13 * sizeof(int64_t));
   out[0] = A->last_variant;
-  if (A->last_variant == 4 || A->last_variant == 5) {
-    out[1] = A->w_rw; out[2] = A->w_wbits; out[3] = A->w_nunits; out[4] = A->w_nwin; out[5] = A->w_csplit;
-    out[6] = A->w_wgs_per_sweep; out[7] = TCOOW_THREADS; out[8] = TCOO_UNROLL;
-    out[11] = A->w_binbits + 100 * A->w_align;
-    out[12] = A->w_slots;
-  } else if (A->last_variant == 3) {
-    out[1] = A->t_rw; out[2] = A->t_wbits; out[3] = A->t_nunits; out[4] = A->t_nwin; out[6] = A->t_wgs_per_sweep;
-    out[7] = HIPEIG_BLOCK; out[8] = TCOO_UNROLL;
+  const bool wg = A->last_variant == 4 || A->last_variant == 5;
+  if (wg || A->last_variant == 3) {
+    const BlockedLayout& L = wg ? A->w : A->t;
+    out[1] = L.rw; out[2] = L.wbits; out[3] = L.nunits; out[4] = L.nwin; out[6] = L.wgs_per_sweep;
+    out[7] = wg ? TCOOW_THREADS : HIPEIG_BLOCK; out[8] = TCOO_UNROLL;
   }
+  if (wg) { out[5] = A->w.csplit; out[11] = A->w.binbits + 100 * A->w.align; out[12] = A->w.slots; }
   if (A->col_stride > 0) { out[9] = A->gl.nchunks; out[10] = A->gl.h; }
   return 0;
 }
