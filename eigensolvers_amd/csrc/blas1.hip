@@ -1463,11 +1463,27 @@ static int arnoldi_side_streams(hipeig_ctx* c) {
   if (ns < 1) ns = 1;
   if (ns > 16) ns = 16;
   if (ns > 1) {
-    HIPEIG_CHECK(hipMalloc((void**)&c->d_arn_ws, (size_t)ns * ARN_SIDE_DOUBLES * sizeof(double)));
-    HIPEIG_CHECK(hipMalloc((void**)&c->d_arn_cnt, (size_t)ns * HIPEIG_TICKET_WORDS * sizeof(unsigned)));
-    HIPEIG_CHECK(hipMemset(c->d_arn_cnt, 0, (size_t)ns * HIPEIG_TICKET_WORDS * sizeof(unsigned)));
-    for (int k = 0; k < ns; ++k) HIPEIG_CHECK(hipStreamCreateWithFlags(&c->arn_stream[k], hipStreamNonBlocking));
-    for (int k = 0; k < 16; ++k) HIPEIG_CHECK(hipEventCreateWithFlags(&c->ev_arn_in[k], hipEventDisableTiming));
+    // all or nothing: a failure halfway releases what was created, so that arn_nstreams == 0 again means "nothing held"
+    // and the next call starts from scratch instead of allocating over live workspaces
+    hipError_t e = hipMalloc((void**)&c->d_arn_ws, (size_t)ns * ARN_SIDE_DOUBLES * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_arn_cnt, (size_t)ns * HIPEIG_TICKET_WORDS * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(c->d_arn_cnt, 0, (size_t)ns * HIPEIG_TICKET_WORDS * sizeof(unsigned));
+    for (int k = 0; k < ns && e == hipSuccess; ++k) e = hipStreamCreateWithFlags(&c->arn_stream[k], hipStreamNonBlocking);
+    for (int k = 0; k < 16 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&c->ev_arn_in[k], hipEventDisableTiming);
+    if (e != hipSuccess) {
+      hipeig_set_error("%s:%d: creating %d Arnoldi side streams -> %s", __FILE__, __LINE__, ns, hipGetErrorString(e));
+      for (int k = 0; k < 16; ++k) {
+        if (c->ev_arn_in[k]) (void)hipEventDestroy(c->ev_arn_in[k]);
+        if (c->arn_stream[k]) (void)hipStreamDestroy(c->arn_stream[k]);
+        c->ev_arn_in[k] = nullptr;
+        c->arn_stream[k] = nullptr;
+      }
+      if (c->d_arn_cnt) (void)hipFree(c->d_arn_cnt);
+      if (c->d_arn_ws) (void)hipFree(c->d_arn_ws);
+      c->d_arn_cnt = nullptr;
+      c->d_arn_ws = nullptr;
+      return 1;
+    }
   }
   c->arn_nstreams = ns;
   return 0;

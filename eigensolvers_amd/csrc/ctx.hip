@@ -150,7 +150,10 @@ extern "C" int hipeig_vec_alloc(hipeig_ctx* c, int64_t n, double** out) {
 
 extern "C" int hipeig_vec_free(hipeig_ctx* c, double* v) {
   if (!v) return 0;
-  // pending kernels on the compute stream may still read v
+  // pending kernels may still read or write v: on the compute stream, and on the Arnoldi side streams (a split step
+  // that has not been collected yet writes its slot's w there)
+  for (int k = 0; k < 16; ++k)
+    if (c->arn_stream[k]) HIPEIG_CHECK(hipStreamSynchronize(c->arn_stream[k]));
   if (hipeig_sync_checked(c)) return 4;
   HIPEIG_CHECK(hipFree(v));
   return 0;
