@@ -1203,6 +1203,7 @@ struct ArnBatchItem {
 };
 #define ARN_SLOT_DOUBLES 128
 
+template <bool PAIR>
 __global__ void __launch_bounds__(ARN_SMALL_THREADS)
 arnoldi_small_batch_kernel(int n, const ArnBatchItem* __restrict__ items, double* __restrict__ slots) {
   __shared__ double lds[32];
@@ -1213,7 +1214,7 @@ arnoldi_small_batch_kernel(int n, const ArnBatchItem* __restrict__ items, double
   double* wre = it->wre;
   double* wim = it->wim;
   __syncthreads();
-  arnoldi_small_body<true>(n, m, ArnColsLds{tab}, wre, wim, slots + (size_t)blockIdx.x * ARN_SLOT_DOUBLES, lds);
+  arnoldi_small_body<PAIR>(n, m, ArnColsLds{tab}, wre, wim, slots + (size_t)blockIdx.x * ARN_SLOT_DOUBLES, lds);
 }
 
 // the step is ONE workgroup (arnoldi_small_kernel): it only WRITES its scalars, so they can go straight to mapped host memory
@@ -1650,10 +1651,13 @@ extern "C" int hipeig_pair_arnoldi_step_p(hipeig_ctx* c, int64_t n, int m, const
 // Split form for several independent steps in a row (the right-hand sides of a lock-step block solve each orthogonalise
 // against their OWN basis): `begin` enqueues the step and an asynchronous copy of its scalars into pinned slot `slot`
 // (0..15, up to 126 doubles each), `end` waits for the stream and hands them over - the host work of one right-hand side
-// then overlaps the kernels of the next instead of the GPU idling at every step's round trip.
-extern "C" int hipeig_pair_arnoldi_step_begin(hipeig_ctx* c, int64_t n, int m, const double* const* Vre, const double* const* Vim,
-                                              double* wre, double* wim, int cols_per_pass, int slot) {
-  HIPEIG_REQUIRE(slot >= 0 && slot < 16 && m >= 0 && 2 * m + 2 <= ARN_SLOT_DOUBLES - 2, "bad slot / too many columns for the split form");
+// then overlaps the kernels of the next instead of the GPU idling at every step's round trip.  Real steps (PAIR = false,
+// m + 2 scalars) and complex pairs (2m + 2) share the slots, the side streams and their workspaces.
+template <bool PAIR>
+static int arnoldi_step_begin_impl(hipeig_ctx* c, int64_t n, int m, const double* const* Vre, const double* const* Vim,
+                                   double* wre, double* wim, int cols_per_pass, int slot) {
+  constexpr int W = PAIR ? 2 : 1;
+  HIPEIG_REQUIRE(slot >= 0 && slot < 16 && m >= 0 && W * m + 2 <= ARN_SLOT_DOUBLES - 2, "bad slot / too many columns for the split form");
   HIPEIG_REQUIRE(!c->collectives, "the split form is for one GPU");
   HIPEIG_REQUIRE(cols_per_pass == 1 || cols_per_pass == 4, "cols_per_pass must be 1 or 4");
   double* dres = c->d_scalars + 2560;
@@ -1673,28 +1677,39 @@ extern "C" int hipeig_pair_arnoldi_step_begin(hipeig_ctx* c, int64_t n, int m, c
       double* res = base + ARN_SIDE_PARTIALS + 64;
       HIPEIG_CHECK(hipEventRecord(c->ev_arn_in[slot], c->stream));
       HIPEIG_CHECK(hipStreamWaitEvent(sp.stream, c->ev_arn_in[slot], 0));
-      if (arnoldi_blocked<true>(c, sp, n, m, Vre, Vim, wre, wim, res)) return 4;
-      HIPEIG_CHECK(hipMemcpyAsync(c->h_scalars + 2048 + (size_t)slot * ARN_SLOT_DOUBLES, res, sizeof(double) * (2 * m + 2),
+      if (arnoldi_blocked<PAIR>(c, sp, n, m, Vre, Vim, wre, wim, res)) return 4;
+      HIPEIG_CHECK(hipMemcpyAsync(c->h_scalars + 2048 + (size_t)slot * ARN_SLOT_DOUBLES, res, sizeof(double) * (W * m + 2),
                                   hipMemcpyDeviceToHost, sp.stream));
       HIPEIG_CHECK(hipEventRecord(c->ev_slot[slot], sp.stream));
       return 0;
     }
   }
-  if (blocked ? arnoldi_blocked<true>(c, arnoldi_main_space(c), n, m, Vre, Vim, wre, wim, dres) : arnoldi_fused<true>(c, n, m, Vre, Vim, wre, wim, dres)) return 4;
+  if (blocked ? arnoldi_blocked<PAIR>(c, arnoldi_main_space(c), n, m, Vre, Vim, wre, wim, dres) : arnoldi_fused<PAIR>(c, n, m, Vre, Vim, wre, wim, dres)) return 4;
   if (!direct)
-    HIPEIG_CHECK(hipMemcpyAsync(c->h_scalars + 2048 + (size_t)slot * ARN_SLOT_DOUBLES, dres, sizeof(double) * (2 * m + 2),
+    HIPEIG_CHECK(hipMemcpyAsync(c->h_scalars + 2048 + (size_t)slot * ARN_SLOT_DOUBLES, dres, sizeof(double) * (W * m + 2),
                                 hipMemcpyDeviceToHost, c->stream));
   HIPEIG_CHECK(hipEventRecord(c->ev_slot[slot], c->stream));
   return 0;
 }
 
+extern "C" int hipeig_pair_arnoldi_step_begin(hipeig_ctx* c, int64_t n, int m, const double* const* Vre, const double* const* Vim,
+                                              double* wre, double* wim, int cols_per_pass, int slot) {
+  return arnoldi_step_begin_impl<true>(c, n, m, Vre, Vim, wre, wim, cols_per_pass, slot);
+}
+
+extern "C" int hipeig_arnoldi_step_begin(hipeig_ctx* c, int64_t n, int m, const double* const* V, double* w, int cols_per_pass, int slot) {
+  return arnoldi_step_begin_impl<false>(c, n, m, V, nullptr, w, nullptr, cols_per_pass, slot);
+}
+
 // `count` (<= 16) such steps of length n <= 8192 in one launch (arnoldi_small_batch_kernel): step i has m[i] columns
-// Vre[i * 64 + j], Vim[i * 64 + j] (tables of 64 entries per step), works on (wre[i], wim[i]) and reports into pinned
-// slot i; collect with hipeig_arnoldi_step_end(slot i).  Needs the mapped scalar area (returns 5 without it or for longer
-// vectors: the caller then takes the step-by-step form).
-extern "C" int hipeig_pair_arnoldi_step_batch_begin(hipeig_ctx* c, int64_t n, int count, const int* m, const double* const* Vre,
-                                                    const double* const* Vim, double* const* wre, double* const* wim) {
-  HIPEIG_REQUIRE(count >= 1 && count <= 16 && m && Vre && Vim && wre && wim, "bad arguments");
+// Vre[i * 64 + j] (and Vim[i * 64 + j] for pairs; tables of 64 entries per step), works on wre[i] (and wim[i]) and reports
+// into pinned slot i; collect with hipeig_arnoldi_step_end(slot i).  Needs the mapped scalar area (returns 5 without it or
+// for longer vectors: the caller then takes the step-by-step form).
+template <bool PAIR>
+static int arnoldi_step_batch_begin_impl(hipeig_ctx* c, int64_t n, int count, const int* m, const double* const* Vre,
+                                         const double* const* Vim, double* const* wre, double* const* wim) {
+  constexpr int W = PAIR ? 2 : 1;
+  HIPEIG_REQUIRE(count >= 1 && count <= 16 && m && Vre && wre && (!PAIR || (Vim && wim)), "bad arguments");
   HIPEIG_REQUIRE(!c->collectives, "the split form is for one GPU");
   if (n > (int64_t)ARN_SMALL_THREADS * ARN_SMALL_E || !c->h_scalars_dev) return 5;
   if (!c->h_arn_items) {
@@ -1710,19 +1725,29 @@ extern "C" int hipeig_pair_arnoldi_step_batch_begin(hipeig_ctx* c, int64_t n, in
   HIPEIG_CHECK(hipEventSynchronize(c->ev_slot[0]));
   ArnBatchItem* items = (ArnBatchItem*)c->h_arn_items;
   for (int i = 0; i < count; ++i) {
-    HIPEIG_REQUIRE(m[i] >= 0 && m[i] <= ARN_SMALL_MAXCOLS && 2 * m[i] + 2 <= ARN_SLOT_DOUBLES - 2, "too many columns for the split form");
+    HIPEIG_REQUIRE(m[i] >= 0 && m[i] <= ARN_SMALL_MAXCOLS && W * m[i] + 2 <= ARN_SLOT_DOUBLES - 2, "too many columns for the split form");
     items[i].m = m[i]; items[i].pad = 0;
-    items[i].wre = wre[i]; items[i].wim = wim[i];
+    items[i].wre = wre[i]; items[i].wim = PAIR ? wim[i] : nullptr;
     for (int j = 0; j < m[i]; ++j) {
       items[i].re[j] = Vre[(size_t)i * ARN_SMALL_MAXCOLS + j];
-      items[i].im[j] = Vim[(size_t)i * ARN_SMALL_MAXCOLS + j];
+      items[i].im[j] = PAIR ? Vim[(size_t)i * ARN_SMALL_MAXCOLS + j] : nullptr;
     }
   }
-  hipLaunchKernelGGL(arnoldi_small_batch_kernel, dim3(count), dim3(ARN_SMALL_THREADS), 0, c->stream, (int)n,
+  hipLaunchKernelGGL((arnoldi_small_batch_kernel<PAIR>), dim3(count), dim3(ARN_SMALL_THREADS), 0, c->stream, (int)n,
                      (const ArnBatchItem*)c->d_arn_items, c->h_scalars_dev + 2048);
   HIPEIG_CHECK(hipGetLastError());
   for (int i = 0; i < count; ++i) HIPEIG_CHECK(hipEventRecord(c->ev_slot[i], c->stream));
   return 0;
+}
+
+extern "C" int hipeig_pair_arnoldi_step_batch_begin(hipeig_ctx* c, int64_t n, int count, const int* m, const double* const* Vre,
+                                                    const double* const* Vim, double* const* wre, double* const* wim) {
+  return arnoldi_step_batch_begin_impl<true>(c, n, count, m, Vre, Vim, wre, wim);
+}
+
+extern "C" int hipeig_arnoldi_step_batch_begin(hipeig_ctx* c, int64_t n, int count, const int* m, const double* const* V,
+                                               double* const* w) {
+  return arnoldi_step_batch_begin_impl<false>(c, n, count, m, V, nullptr, w, nullptr);
 }
 
 extern "C" int hipeig_arnoldi_step_end(hipeig_ctx* c, int slot, int count, double* out) {

@@ -186,6 +186,22 @@ struct ShiftPairBlockEpilogue {
   }
 };
 
+// The real shift of a lock-step GCROT solve, y_j = sign*(sigma*x_j - (H X)_j) (numpyVector.py:152/161 for the nBlock
+// right-hand sides of inexact_Lanczos.py:319-320), with the roundings of AxpyEpilogue (spmv.hip): the shift term and the
+// operator sum separately, then their sum - a column differs from hipeig_spmv_shift only through the operator sum.
+// a_self = sign*sigma, a_sum = -sign; xl: the packed operand block restricted to this operator's rows.
+template <int K>
+struct ShiftBlockEpilogue {
+  double a_self, a_sum;
+  const double* __restrict__ xl;
+  double* __restrict__ Y;
+  __device__ __forceinline__ void elem(int64_t r, int j, double sum, double& acc) const {
+    const int64_t i = r * K + j;
+    const double t = (a_self == 0.0) ? 0.0 : mul_rn(a_self, xl[i]);
+    Y[i] = add_rn(t, mul_rn(a_sum, sum));
+  }
+};
+
 template <int K, class Epi>
 __global__ void __launch_bounds__(BCOO_THREADS)
 spmm_bcoo_kernel(BcooView T, const double* __restrict__ X, Epi epi) {
@@ -270,6 +286,39 @@ extern "C" int hipeig_spmm(hipeig_ctx* c, hipeig_csr* A, int k, const double* co
     const int kk = (k - j0 < K) ? k - j0 : K;
     if (hipeig_block_pack(c, K, nx, kk, X + j0, Xi)) return 1;
     if (K == 4 ? spmm_block_impl<4>(c, A, Xi, Yi) : spmm_block_impl<8>(c, A, Xi, Yi)) return 1;
+    if (hipeig_block_unpack(c, K, ny, kk, Yi, Y + j0)) return 1;
+    j0 += kk;
+  }
+  return 0;
+}
+
+// The real shifted operator of the lock-step GCROT solves (the nBlock solves of one block Lanczos iteration share operator
+// and shift, inexact_Lanczos.py:319-320): Y_j = sign*(sigma*X_j - H X_j), j < k, the shift applied in the block product's
+// epilogue.  Kernel choice, chunking (8 operands per pass, 4 for a remainder of <= 4) and the contexts taken are those of
+// hipeig_spmm; a context without a block exchange runs hipeig_spmv_shift per operand.
+extern "C" int hipeig_spmm_shift(hipeig_ctx* c, hipeig_csr* A, int k, double sigma, double sign,
+                                 const double* const* X, double* const* Y) {
+  HIPEIG_REQUIRE(k >= 1 && X && Y, "bad arguments");
+  HIPEIG_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
+  if (A->nrows == 0) return 0;
+  if (c->collectives && !c->comm && !c->loop) {
+    for (int j = 0; j < k; ++j)
+      if (hipeig_spmv_shift(c, A, sigma, sign, X[j], Y[j])) return 1;
+    return 0;
+  }
+  const int64_t nx = c->collectives ? A->nrows : A->ncols;
+  const int64_t ny = A->nrows;
+  const int64_t xoff = c->collectives ? 0 : A->row_offset;      // the shift term reads this operator's rows of the block
+  if (ensure_blk_ws(c, (size_t)(nx + ny) * BCOO_KMAX)) return 1;
+  double* Xi = c->blk_ws;
+  double* Yi = c->blk_ws + (size_t)nx * BCOO_KMAX;
+  const double a_self = sign * sigma, a_sum = -sign;
+  for (int j0 = 0; j0 < k;) {
+    const int K = (k - j0 <= 4) ? 4 : 8;
+    const int kk = (k - j0 < K) ? k - j0 : K;
+    if (hipeig_block_pack(c, K, nx, kk, X + j0, Xi)) return 1;
+    if (K == 4 ? spmm_block_run<4>(c, A, Xi, ShiftBlockEpilogue<4>{a_self, a_sum, Xi + xoff * 4, Yi})
+               : spmm_block_run<8>(c, A, Xi, ShiftBlockEpilogue<8>{a_self, a_sum, Xi + xoff * 8, Yi})) return 1;
     if (hipeig_block_unpack(c, K, ny, kk, Yi, Y + j0)) return 1;
     j0 += kk;
   }

@@ -78,6 +78,41 @@ class _Ops:
                   out.ctypes.data_as(C.POINTER(C.c_double)), self.cols_per_pass)
         return float(np.sqrt(out[0])), out[1:m + 1], float(np.sqrt(out[m + 1]))
 
+    def arnoldi_begin(self, vs, w, slot):
+        """Enqueue the step without waiting for its scalars (pinned slot ``slot``); ``arnoldi_end`` collects them."""
+        m = len(vs)
+        tab = (C.c_void_p * max(m, 1))(*[v.ptr for v in vs])
+        _lib.call("hipeig_arnoldi_step_begin", self.h, self.n, m, C.cast(tab, C.POINTER(C.c_void_p)), w.ptr,
+                  self.cols_per_pass, int(slot))
+
+    def arnoldi_end(self, m, slot):
+        out = np.empty(m + 2)
+        _lib.call("hipeig_arnoldi_step_end", self.h, int(slot), m + 2, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return float(np.sqrt(out[0])), out[1:m + 1], float(np.sqrt(out[m + 1]))
+
+    SPLIT_MAX_COLS = 124         # m + 2 doubles must fit a pinned slot (hipeig.h)
+    BATCH_MAX_N = 8192           # lengths at which a step is ONE workgroup: several steps share a launch
+    BATCH_MAX_COLS = 64          # columns a batched step takes
+
+    @staticmethod
+    def arnoldi_begin_batch(opss, reqs):
+        """The steps ``reqs = [(columns, w), ...]`` of up to 16 right-hand sides in one launch, a workgroup each (slots
+        0, 1, ...; collect with ``arnoldi_end``).  Returns False, having done nothing, when the library declines (vectors
+        longer than one workgroup handles)."""
+        cnt, r = len(reqs), opss[0]
+        ms = (C.c_int * cnt)(*[len(vs) for vs, _ in reqs])
+        tab = (C.c_void_p * (64 * cnt))()
+        for i, (vs, _) in enumerate(reqs):
+            for j, v in enumerate(vs):
+                tab[64 * i + j] = v.ptr
+        ws = (C.c_void_p * cnt)(*[w.ptr for _, w in reqs])
+        PP = C.POINTER(C.c_void_p)
+        rc = getattr(_lib.load(), "hipeig_arnoldi_step_batch_begin")(r.h, r.n, cnt, ms, C.cast(tab, PP), C.cast(ws, PP))
+        if rc == 5:
+            return False
+        _lib.check(rc, "hipeig_arnoldi_step_batch_begin")
+        return True
+
     def combine(self, coeffs, vecs):
         """sum_i coeffs[i] * vecs[i] in one pass."""
         out = self.new()
@@ -187,6 +222,7 @@ class _PairOps:
 
     SPLIT_MAX_COLS = 62          # 2m + 2 doubles must fit a pinned slot (hipeig.h)
     BATCH_MAX_N = 8192           # lengths at which a step is ONE workgroup: several steps share a launch
+    BATCH_MAX_COLS = 64          # columns a batched step takes
 
     @staticmethod
     def arnoldi_begin_batch(opss, reqs):
@@ -366,7 +402,8 @@ def gcrotmk_device_block(ctx, block_matvec, bs, n, rtol=1e-5, atol=0.0, maxiter=
     unchanged - its own Krylov spaces, its own recycle pairs, its own stopping - but their operator applications are
     collected and handed to ``block_matvec([v_0, v_1, ...]) -> [A v_0, A v_1, ...]`` together, so that they run as block
     products (one pass over the operator for several vectors).  The right-hand sides of one FEAST contour point share
-    operator and shift (feast.py:198-200).  A solve that has finished simply drops out of the block.
+    operator and shift (feast.py:198-200), and so do the nBlock solves of one block Lanczos iteration
+    (inexact_Lanczos.py:319-320).  A solve that has finished simply drops out of the block.
     Returns ``[(x, info, stats), ...]`` in the order of ``bs``."""
     results = [None] * len(bs)
     stats = [{"outer": 0, "matvecs": 0} for _ in bs]
@@ -387,17 +424,18 @@ def gcrotmk_device_block(ctx, block_matvec, bs, n, rtol=1e-5, atol=0.0, maxiter=
         opss.append(ops)
         gens.append(_gcrotmk(ops, ctx, b, n, rtol, atol, maxiter, m, k, complex_pairs, None, stats[i]))
         advance(i, first=True)
-    split = complex_pairs and all(hasattr(o, "arnoldi_begin") for o in opss)      # the split (begin / end) step exists for device pairs
-    batched = split and ops_factory is None and n <= _PairOps.BATCH_MAX_N and all(o.cols_per_pass in (1, 4) for o in opss)
+    kind = _PairOps if complex_pairs else _Ops
+    split = all(hasattr(o, "arnoldi_begin") for o in opss)      # the split (begin / end) step exists for the device ops
+    batched = split and ops_factory is None and n <= kind.BATCH_MAX_N and all(o.cols_per_pass in (1, 4) for o in opss)
     while req:
         # the orthogonalisation steps of all right-hand sides that wait for one: enqueued back to back, collected
         # afterwards, so that the host work of one (QR insert, bookkeeping) runs under the kernels of the next
         arn = sorted(i for i, r in req.items() if r[0] == "arn")
         while arn:
             batch = arn[:16]
-            if split and all(len(req[i][1]) <= _PairOps.SPLIT_MAX_COLS for i in batch):
-                if not (batched and len(batch) > 1 and
-                        _PairOps.arnoldi_begin_batch([opss[i] for i in batch], [(req[i][1], req[i][2]) for i in batch])):
+            if split and all(len(req[i][1]) <= kind.SPLIT_MAX_COLS for i in batch):
+                if not (batched and len(batch) > 1 and all(len(req[i][1]) <= kind.BATCH_MAX_COLS for i in batch) and
+                        kind.arnoldi_begin_batch([opss[i] for i in batch], [(req[i][1], req[i][2]) for i in batch])):
                     for slot, i in enumerate(batch):
                         opss[i].arnoldi_begin(req[i][1], req[i][2], slot)
                 for slot, i in enumerate(batch):

@@ -21,6 +21,11 @@ from . import _lib
 from .abstract_vector import AbstractVector, LINDEP_DEFAULT_VALUE
 
 _ORTHO_METHODS = {"mgs": 0, "cgs2": 1}
+# GCROT solves with a real shift run in lock step (HipVector._solve_real_block) from BLOCK_SOLVE_MIN_GCROT right-hand sides
+# on where a vector fits the one-launch Arnoldi batch (n <= gcrotmk._Ops.BATCH_MAX_N), from BLOCK_SOLVE_MIN_GCROT_LONG on
+# beyond it (measured: tools/gcrot_block_bench.py, profiles/r06_gcrot_block_bench.jsonl).
+BLOCK_SOLVE_MIN_GCROT = 2
+BLOCK_SOLVE_MIN_GCROT_LONG = 4
 
 
 def _ptr_table(bufs):
@@ -43,6 +48,7 @@ class HipContext:
         self.nranks, self.rank = 1, 0
         self.direct_only = False         # a communicator without RCCL (attach_direct_only): no exchange for block operands
         self.partitioned = True          # False in replica mode (set_partitioned): whole operators / vectors on every rank
+        self._force_collectives = None   # HIPEIG_FORCE_COLLECTIVES as the library read it when a communicator was attached
         self._pool = {}
         self._finalizer = weakref.finalize(self, HipContext._destroy, h, self._pool)
 
@@ -72,11 +78,23 @@ class HipContext:
         buf = C.create_string_buffer(bytes(unique_id), 128)
         _lib.call("hipeig_comm_init", self.handle, int(nranks), int(rank), C.cast(buf, C.c_void_p))
         self.nranks, self.rank = int(nranks), int(rank)
+        self._note_comm()
 
     def attach_loopback(self, group_handle, nranks, rank):
         """Join an in-process loopback group (``distributed.LoopbackGroup``)."""
         _lib.call("hipeig_comm_init_loopback", self.handle, group_handle, int(rank))
         self.nranks, self.rank = int(nranks), int(rank)
+        self._note_comm()
+
+    def _note_comm(self):
+        self._force_collectives = os.environ.get("HIPEIG_FORCE_COLLECTIVES", "0") not in ("", "0")
+
+    @property
+    def collectives(self):
+        """Products and reductions go through the communicator: a row-partitioned run of several ranks, or one rank with
+        HIPEIG_FORCE_COLLECTIVES=1 at attach time (the library's flag, comm.hip)."""
+        return (self._force_collectives is not None and self.partitioned
+                and (self.nranks > 1 or self._force_collectives))
 
     # ---- operand exchange of a row-partitioned product -------------------------------------------
     GATHER_BACKENDS = {0: "rccl", 1: "direct"}
@@ -112,6 +130,7 @@ class HipContext:
         _lib.call("hipeig_comm_init_direct", self.handle, int(nranks), int(rank))
         self.nranks, self.rank = int(nranks), int(rank)
         self.direct_only = True
+        self._note_comm()
 
     def set_gather_backend(self, name):
         code = {v: k for k, v in self.GATHER_BACKENDS.items()}[name]
@@ -391,6 +410,15 @@ class HipCsrOperator:
     def apply_shifted(self, sigma, x, y, reverse=False):
         _lib.call("hipeig_spmv_shift", self.ctx.handle, self.handle, float(sigma),
                   -1.0 if reverse else 1.0, x.ptr, y.ptr)
+
+    def apply_shifted_block(self, sigma, xs, reverse=False):
+        """[sign*(sigma*x - H x) for x in xs] for real operands and a real shift (the operator of the lock-step GCROT
+        solves): eight operands share one pass over the operator (``hipeig_spmm_shift``).  Returns new buffers."""
+        ys = [self.ctx.alloc(self.nrows) for _ in xs]
+        xt, keep1 = _ptr_table(xs)
+        yt, keep2 = _ptr_table(ys)
+        _lib.call("hipeig_spmm_shift", self.ctx.handle, self.handle, len(xs), float(sigma), -1.0 if reverse else 1.0, xt, yt)
+        return ys
 
     def apply_shifted_pair(self, z, xr, xi, yr, yi, reverse=False):
         """(yr, yi) = sign*(z*x - H x) for the complex operand x = xr + i xi and the complex shift z (the operator is
@@ -683,15 +711,28 @@ class HipVector(AbstractVector):
         once per block vector on the same operator and shift).  Every column runs the recurrences and
         stopping tests of the single solve; results, ``last_solve_stats`` and the exception on
         non-convergence (numpyVector.py:175-177) are those of the one-by-one calls.  Blocks of <= 4 use a
-        4-wide interleave (twice the rows per workgroup), larger ones chunks of 8.  Solvers other than MINRES,
-        complex shifts and fewer than ``BLOCK_SOLVE_MIN`` right-hand sides take the one-by-one calls."""
+        4-wide interleave (twice the rows per workgroup), larger ones chunks of 8.  GCROT runs its solves in lock step
+        too, for a complex shift (``_solve_complex_block``) and for a real one from ``BLOCK_SOLVE_MIN_GCROT`` right-hand
+        sides on, ``BLOCK_SOLVE_MIN_GCROT_LONG`` for vectors longer than one Arnoldi batch (n > 8192;
+        ``_solve_real_block``; not with ``options["blockSolve"] = False``).  A context with collectives solves one by one.  Other solvers, an initial guess
+        and fewer right-hand sides take the one-by-one calls."""
         bs = list(bs)
         o = bs[0].options["linearSystemArgs"]
-        if (o["linearSolver"] == "gcrotmk" and (isinstance(sigma, complex) or np.iscomplexobj(sigma)) and x0 is None
-                and len(bs) >= 2 and isinstance(H, HipCsrOperator) and not bs[0].ctx.direct_only
-                and (bs[0].ctx.nranks == 1 or not bs[0].ctx.partitioned)       # whole vectors: one GPU, or FEAST's contour replicas
-                and all(isinstance(b, HipVector) for b in bs)):
+        complex_shift = isinstance(sigma, complex) or np.iscomplexobj(sigma)
+
+        def whole():
+            # whole vectors on a context without collectives (one GPU, or FEAST's contour replicas): the split Arnoldi steps
+            # run on one GPU only; a row partition - or one rank rehearsing it with HIPEIG_FORCE_COLLECTIVES - solves one by one
+            return (isinstance(H, HipCsrOperator) and not bs[0].ctx.direct_only and not bs[0].ctx.collectives
+                    and all(isinstance(b, HipVector) for b in bs))
+
+        if o["linearSolver"] == "gcrotmk" and complex_shift and x0 is None and len(bs) >= 2 and whole():
             return HipVector._solve_complex_block(H, bs, complex(sigma), o, reverseGF)
+        if (o["linearSolver"] == "gcrotmk" and not complex_shift and x0 is None and bs[0].options.get("blockSolve", True)
+                and whole()):
+            from .gcrotmk import _Ops
+            if len(bs) >= (BLOCK_SOLVE_MIN_GCROT if len(bs[0]) <= _Ops.BATCH_MAX_N else BLOCK_SOLVE_MIN_GCROT_LONG):
+                return HipVector._solve_real_block(H, bs, float(sigma), o, reverseGF)
         if (o["linearSolver"] != "minres" or isinstance(sigma, complex) or np.iscomplexobj(sigma)
                 or x0 is not None or len(bs) < HipVector.BLOCK_SOLVE_MIN or not isinstance(H, HipCsrOperator)
                 or bs[0].ctx.direct_only):
@@ -824,6 +865,36 @@ class HipVector(AbstractVector):
         for b, (x, conv, gstats) in zip(bs, sols):
             res = HipComplexVector(b._new(x[0]), b._new(x[1]))
             res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"]}
+            failed = failed or conv != 0
+            out.append(res)
+        if failed:
+            raise UserWarning("Warning:: Iterative solver is not converged ")
+        return out
+
+    @staticmethod
+    def _solve_real_block(H, bs, sigma, o, reverseGF):
+        """The shifted solves sign*(sigma*I - H) x_i = b_i of one block Lanczos iteration (inexact_Lanczos.py:319-320 runs
+        them one after the other on the same operator and real shift) in lock step: each is the GCROT of ``solve``,
+        unchanged - its own spaces, its own stopping - but their operator applications run as block products, eight
+        operands per pass over the operator (``gcrotmk_device_block``, ``hipeig_spmm_shift``), and their Arnoldi steps are
+        enqueued back to back (one launch for all of them at n <= 8192).  Results, ``last_solve_stats`` (plus
+        ``"lock_step": True``) and the exception on non-convergence, raised once every solve has run, are those of the
+        one-by-one solves."""
+        from .gcrotmk import gcrotmk_device_block
+        ctx, n = bs[0].ctx, bs[0]._buf.n
+        H.honour_reduction_option(bs[0].options)
+
+        def block_matvec(vs):
+            return H.apply_shifted_block(sigma, vs, reverse=reverseGF)
+
+        sols = gcrotmk_device_block(ctx, block_matvec, [b._buf for b in bs], n, rtol=float(o["linear_tol"]),
+                                    atol=float(o["linear_atol"]), maxiter=int(o["linearIter"]),
+                                    cols_per_pass=int(o.get("arnoldiColumnsPerPass", 1)))
+        out, failed = [], False
+        for b, (x, conv, gstats) in zip(bs, sols):
+            res = b._new(x)
+            res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"],
+                                                         "lock_step": True}
             failed = failed or conv != 0
             out.append(res)
         if failed:

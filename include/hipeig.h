@@ -189,6 +189,14 @@ int hipeig_pair_arnoldi_step_begin(hipeig_ctx* ctx, int64_t n, int m, const doub
 int hipeig_pair_arnoldi_step_batch_begin(hipeig_ctx* ctx, int64_t n, int count, const int* m, const double* const* Vre,
                                          const double* const* Vim, double* const* wre, double* const* wim);
 int hipeig_arnoldi_step_end(hipeig_ctx* ctx, int slot, int count, double* out);
+/* The real counterparts for the lock-step GCROT solves of a real shift (the nBlock solves of inexact_Lanczos.py:319-320,
+ * each numpyVector.py:161's gcrotmk): begin reports m + 2 doubles [ ||w||^2 before, h_0..h_{m-1}, ||w||^2 after ] into
+ * pinned slot `slot` (m + 2 <= 126), on the side streams and workspaces of the pair form; the batch runs up to 16 steps
+ * of length n <= 8192 in one launch (step i: m[i] <= 64 columns V[64 i + j], vector w[i], slot i) and returns 5, having
+ * done nothing, for longer vectors.  Collect either with hipeig_arnoldi_step_end.  One GPU only.                    */
+int hipeig_arnoldi_step_begin(hipeig_ctx* ctx, int64_t n, int m, const double* const* V, double* w, int cols_per_pass, int slot);
+int hipeig_arnoldi_step_batch_begin(hipeig_ctx* ctx, int64_t n, int count, const int* m, const double* const* V,
+                                    double* const* w);
 
 /* ---- sparse operator: replaces the scipy.sparse / ndarray H handed to the loop ----- */
 /* Host CSR -> device.  rowptr has nrows+1 entries (local rows), col holds GLOBAL column
@@ -249,6 +257,12 @@ int hipeig_csr_pair_info(hipeig_csr* A, int64_t out[2]);
  * Y[j] = H X[j], j < k.  Internally the operands are interleaved so that each non-zero costs
  * one index fetch and one contiguous gather for all k (tall-skinny SpMM).                   */
 int hipeig_spmm(hipeig_ctx* ctx, hipeig_csr* A, int k, const double* const* X, double* const* Y);
+/* The LinearOperator lambda of solve() (numpyVector.py:152,161) for the nBlock right-hand sides of one block Lanczos
+ * iteration, which share operator and real shift (inexact_Lanczos.py:319-320): Y[j] = sign*(sigma*X[j] - H X[j]), j < k,
+ * as block products whose epilogue applies the shift with hipeig_spmv_shift's roundings.  Kernel choice, chunking and
+ * the contexts taken are those of hipeig_spmm.                                                                        */
+int hipeig_spmm_shift(hipeig_ctx* ctx, hipeig_csr* A, int k, double sigma, double sign,
+                      const double* const* X, double* const* Y);
 /* The complex matvec of the contour solves for SEVERAL right-hand sides (feast.py:198-200: the m0 solves of a contour point
  * share operator and shift): Y_p = sign*(z*X_p - H X_p), p < npairs, the complex operands as (re, im) buffers.  Four operands
  * share one pass over the operator (an 8-wide block product whose epilogue applies the shift).                        */
