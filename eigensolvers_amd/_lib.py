@@ -99,6 +99,7 @@ SIGNATURES = {
     "hipeig_spmm": [_P, _P, C.c_int, _PP, _PP],
     "hipeig_spmm_shift": [_P, _P, C.c_int, _D, _D, _PP, _PP],
     "hipeig_spmm_shift_pairs": [_P, _P, C.c_int, _D, _D, _D, _PP, _PP, _PP, _PP],
+    "hipeig_spmm_shift_pairs_z": [_P, _P, C.c_int, _DP, _DP, _D, _PP, _PP, _PP, _PP],
     "hipeig_minres": [_P, _P, _D, _D, _P, _P, _D, C.c_int, _IP, _DP],
     "hipeig_minres_x0": [_P, _P, _D, _D, _P, _P, _P, _D, C.c_int, _IP, _DP],
     "hipeig_dense_solve_small": [_P, _P, _D, _D, _D, _P, _P, _P, _P, _IP],

@@ -186,6 +186,33 @@ struct ShiftPairBlockEpilogue {
   }
 };
 
+// The same product with a shift PER OPERAND: the solves of different contour points are independent (feast.py:189-200),
+// so one block may carry operands of several points.  ar[p], ai[p] = sign*zr_p, sign*zi_p of complex operand p (columns
+// 2p, 2p + 1); the operator sum of a column does not depend on the shift, and per element the arithmetic and its roundings
+// are those of ShiftPairBlockEpilogue.  The operand index is a per-thread value: the shift is picked by an unrolled
+// compare chain over the kernel arguments (selects between scalar registers, no indexed copy of the array in scratch).
+template <int K>
+struct ShiftPairsZBlockEpilogue {
+  double ar[K / 2], ai[K / 2];                         // sign*zr_p, sign*zi_p; unused operands: 0
+  double as;                                           // -sign
+  const double* __restrict__ xl;
+  double* __restrict__ Y;
+  __device__ __forceinline__ void elem(int64_t r, int j, double sum, double& acc) const {
+    const int p = j >> 1;
+    double a_r = ar[0], a_i = ai[0];
+#pragma unroll
+    for (int q = 1; q < K / 2; ++q) {
+      a_r = (p == q) ? ar[q] : a_r;
+      a_i = (p == q) ? ai[q] : a_i;
+    }
+    const int64_t base = r * K + (j & ~1);
+    const double vr = xl[base], vi = xl[base + 1];
+    const double own = (j & 1) ? vi : vr;
+    const double t = add_rn(mul_rn(a_r, own), mul_rn(as, sum));
+    Y[r * K + j] = (j & 1) ? fma(a_i, vr, t) : fma(-a_i, vi, t);
+  }
+};
+
 // The real shift of a lock-step GCROT solve, y_j = sign*(sigma*x_j - (H X)_j) (numpyVector.py:152/161 for the nBlock
 // right-hand sides of inexact_Lanczos.py:319-320), with the roundings of AxpyEpilogue (spmv.hip): the shift term and the
 // operator sum separately, then their sum - a column differs from hipeig_spmv_shift only through the operator sum.
@@ -325,19 +352,29 @@ extern "C" int hipeig_spmm_shift(hipeig_ctx* c, hipeig_csr* A, int k, double sig
   return 0;
 }
 
+template <int K>
+static ShiftPairsZBlockEpilogue<K> shift_pairs_z_epilogue(const double* zr, const double* zi, int np, double sign,
+                                                          const double* xl, double* Y) {
+  ShiftPairsZBlockEpilogue<K> e{};
+  for (int p = 0; p < np && p < K / 2; ++p) { e.ar[p] = sign * zr[p]; e.ai[p] = sign * zi[p]; }
+  e.as = -sign; e.xl = xl; e.Y = Y;
+  return e;
+}
+
 // The complex matvec of the contour solves for SEVERAL right-hand sides at once (feast.py:198-200: the m0 solves of one
 // contour point share operator and shift): y_p = sign*(z*x_p - H x_p), p < npairs, complex operands as (re, im) buffers.
 // Four complex operands fill an 8-wide block (two a 4-wide one), so the (index, value) stream of the operator is read
 // once per four operands instead of once each; the shift is applied in the block product's epilogue.  A row-partitioned
 // or direct-only context and npairs = 1 take hipeig_spmv_shift_pair per operand.
-extern "C" int hipeig_spmm_shift_pairs(hipeig_ctx* c, hipeig_csr* A, int npairs, double zr, double zi, double sign,
-                                       const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim) {
-  HIPEIG_REQUIRE(npairs >= 1 && Xre && Xim && Yre && Yim, "bad arguments");
+// zr, zi: one shift for all operands (zstride = 0) or npairs of them (zstride = 1; hipeig_spmm_shift_pairs_z below).
+static int spmm_shift_pairs_impl(hipeig_ctx* c, hipeig_csr* A, int npairs, const double* zr, const double* zi, int zstride, double sign,
+                                 const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim) {
+  HIPEIG_REQUIRE(npairs >= 1 && zr && zi && Xre && Xim && Yre && Yim, "bad arguments");
   HIPEIG_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
   if (A->nrows == 0) return 0;
   if (npairs == 1 || c->collectives) {
     for (int p = 0; p < npairs; ++p)
-      if (hipeig_spmv_shift_pair(c, A, zr, zi, sign, Xre[p], Xim[p], Yre[p], Yim[p])) return 1;
+      if (hipeig_spmv_shift_pair(c, A, zr[p * zstride], zi[p * zstride], sign, Xre[p], Xim[p], Yre[p], Yim[p])) return 1;
     return 0;
   }
   const int64_t nx = A->ncols, ny = A->nrows;
@@ -352,7 +389,7 @@ extern "C" int hipeig_spmm_shift_pairs(hipeig_ctx* c, hipeig_csr* A, int npairs,
   if (ensure_blk_ws(c, (size_t)(nx + ny) * BCOO_KPACK)) return 1;
   double* Xi = c->blk_ws;
   double* Yi = c->blk_ws + (size_t)nx * BCOO_KPACK;
-  const double ar = sign * zr, ai = sign * zi, as = -sign;
+  const double as = -sign;
   for (int p0 = 0; p0 < npairs;) {
     const int left = npairs - p0;
     const int np = (wide == 8 && left > 4) ? (left < 8 ? left : 8) : (left < 4 ? left : 4);
@@ -365,14 +402,32 @@ extern "C" int hipeig_spmm_shift_pairs(hipeig_ctx* c, hipeig_csr* A, int npairs,
     }
     if (hipeig_block_pack(c, K, nx, 2 * np, cols, Xi)) return 1;
     int rc;
-    if (K == 4) rc = spmm_block_run<4>(c, A, Xi, ShiftPairBlockEpilogue<4>{ar, ai, as, Xi + A->row_offset * 4, Yi});
-    else if (K == 8) rc = spmm_block_run<8>(c, A, Xi, ShiftPairBlockEpilogue<8>{ar, ai, as, Xi + A->row_offset * 8, Yi});
-    else rc = spmm_block_run<16>(c, A, Xi, ShiftPairBlockEpilogue<16>{ar, ai, as, Xi + A->row_offset * 16, Yi});
+    if (zstride == 0) {
+      const double ar = sign * zr[0], ai = sign * zi[0];
+      if (K == 4) rc = spmm_block_run<4>(c, A, Xi, ShiftPairBlockEpilogue<4>{ar, ai, as, Xi + A->row_offset * 4, Yi});
+      else if (K == 8) rc = spmm_block_run<8>(c, A, Xi, ShiftPairBlockEpilogue<8>{ar, ai, as, Xi + A->row_offset * 8, Yi});
+      else rc = spmm_block_run<16>(c, A, Xi, ShiftPairBlockEpilogue<16>{ar, ai, as, Xi + A->row_offset * 16, Yi});
+    } else if (K == 4) rc = spmm_block_run<4>(c, A, Xi, shift_pairs_z_epilogue<4>(zr + p0, zi + p0, np, sign, Xi + A->row_offset * 4, Yi));
+    else if (K == 8) rc = spmm_block_run<8>(c, A, Xi, shift_pairs_z_epilogue<8>(zr + p0, zi + p0, np, sign, Xi + A->row_offset * 8, Yi));
+    else rc = spmm_block_run<16>(c, A, Xi, shift_pairs_z_epilogue<16>(zr + p0, zi + p0, np, sign, Xi + A->row_offset * 16, Yi));
     if (rc) return rc;
     if (hipeig_block_unpack(c, K, ny, 2 * np, Yi, outs)) return 1;
     p0 += np;
   }
   return 0;
+}
+
+extern "C" int hipeig_spmm_shift_pairs(hipeig_ctx* c, hipeig_csr* A, int npairs, double zr, double zi, double sign,
+                                       const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim) {
+  return spmm_shift_pairs_impl(c, A, npairs, &zr, &zi, 0, sign, Xre, Xim, Yre, Yim);
+}
+
+// The same with a shift per operand, y_p = sign*(z_p*x_p - H x_p): the solves of ALL contour points of a FEAST iteration
+// are independent (feast.py:189-200), so operands of different points may share a pass over the operator.  zr, zi: host
+// arrays of npairs shifts.  Chunking, the width rule and the per-operand fallbacks are those of hipeig_spmm_shift_pairs.
+extern "C" int hipeig_spmm_shift_pairs_z(hipeig_ctx* c, hipeig_csr* A, int npairs, const double* zr, const double* zi, double sign,
+                                         const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim) {
+  return spmm_shift_pairs_impl(c, A, npairs, zr, zi, 1, sign, Xre, Xim, Yre, Yim);
 }
 
 extern "C" int hipeig_csr_block_info(hipeig_csr* A, int64_t info[4]) {

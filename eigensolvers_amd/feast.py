@@ -116,6 +116,80 @@ def _quadrature_terms_block(cls, Amat, guesses, z, radius, angle, weight, contou
     return [cls.real((-0.50 * weight * radius * phase) * Qe) for Qe in sols]
 
 
+def _contour_pairs(npoints, nsub, contourComm=None, contourDeal="point"):
+    """The (contour point, subspace vector) pairs this rank solves, in point-major order.  ``"point"``: whole contour
+    points round robin (point k on rank ``k % nranks``); ``"balanced"``: pair ``k*nsub + im0`` round robin, so that every
+    rank gets the same mix of points (the points of a contour differ several-fold in the products their solves need)."""
+    if contourDeal not in ("point", "balanced"):
+        raise ValueError(f"unknown contourDeal {contourDeal!r} ('point' or 'balanced')")
+    pairs = [(k, im0) for k in range(npoints) for im0 in range(nsub)]
+    if contourComm is None:
+        return pairs
+    nr, r = contourComm.nranks, contourComm.rank
+    if contourDeal == "balanced":
+        return [(k, im0) for k, im0 in pairs if (k * nsub + im0) % nr == r]
+    return [(k, im0) for k, im0 in pairs if k % nr == r]
+
+
+def _takes_shift_per_operand(cls, b0):
+    """The backend's ``solveBlock`` takes one shift per right-hand side and hands each solution out as its solve ends
+    (``HipVector.solveBlock(..., onSolution=, poolStats=)``)."""
+    import inspect
+    hook = getattr(cls, "solveBlock", None)
+    if hook is None or not b0.hasExactAddition or not getattr(b0, "options", {}).get("blockSolve", True):
+        return False
+    try:
+        return "onSolution" in inspect.signature(hook).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def _pooled_contour_sums(cls, A, Y, pairs, nodes, radius, contourEllipseFactor, status):
+    """The filtered vectors of one FEAST iteration with ALL contour solves of this rank handed to the backend as one job
+    list (the solves of different contour points are independent, feast.py:189-200; the backend keeps an always-full
+    pool of them alive).  ``nodes[k] = (theta, z, weight)``.  Every finished solution becomes its quadrature term with
+    the arithmetic of ``_quadrature_terms_block`` and is added to ``Q[im0]`` in ASCENDING point order - a term that
+    arrives before its predecessor waits - so that, given identical solves, ``Q`` is bit for bit the per-point loop's.
+    A real node keeps today's path; its terms take their place in the same order.  Returns (Q, pool record or None)."""
+    nsub = len(Y)
+    Q = [None] * nsub
+    order = [[k for k, i in pairs if i == im0] for im0 in range(nsub)]
+    held = [dict() for _ in range(nsub)]
+    taken = [0] * nsub
+
+    def arrive(k, im0, term):
+        held[im0][k] = term
+        while taken[im0] < len(order[im0]) and order[im0][taken[im0]] in held[im0]:
+            nxt = held[im0].pop(order[im0][taken[im0]])
+            updateQ(Q, im0, nxt, 0 if Q[im0] is None else 1)
+            taken[im0] += 1
+
+    jobs = []
+    for k, im0 in pairs:
+        theta, z, weight = nodes[k]
+        if abs(z.imag) < 1e-15:
+            status["quadrature"] = k
+            arrive(k, im0, calculateQuadrature(A, Y[im0], z, radius, theta, weight, contourEllipseFactor))
+        else:
+            jobs.append((k, im0))
+    record = {}
+    if jobs:
+        def on_solution(j, Qe):
+            k, im0 = jobs[j]
+            theta, z, weight = nodes[k]
+            status["quadrature"] = k
+            phase = contourEllipseFactor * math.cos(theta) + math.sin(theta) * 1j
+            arrive(k, im0, cls.real((-0.50 * weight * radius * phase) * Qe))
+
+        cls.solveBlock(A, [Y[im0] for k, im0 in jobs], [nodes[k][1] for k, im0 in jobs], opType="gen",
+                       onSolution=on_solution, poolStats=record)
+    if not record:
+        return Q, None
+    return Q, {"width": record["width"], "rounds": record["rounds"],
+               "histogram": dict(sorted(record["histogram"].items())), "pairs": [list(p) for p in jobs],
+               "products": list(record["products"]), "outer": list(record["outer"])}
+
+
 def updateQ(Q, im0, Qquad_k, k):
     """Accumulate the k-th quadrature term into the im0-th filtered vector (feast.py:105-121)."""
     if k == 0:
@@ -127,12 +201,20 @@ def updateQ(Q, im0, Qquad_k, k):
 
 def feastDiagonalization(A, Y, nc, quad, eMin, eMax, eConv, maxit, contourEllipseFactor=1.0,
                          writeOut=True, eShift=0.0, convertUnit="au", outFileName=None,
-                         summaryFileName=None, contourComm=None):
+                         summaryFileName=None, contourComm=None, contourPool=False, contourDeal="point"):
     """Arguments and returns as the reference (feast.py:126-165): ``(ev, Y, status)``.
 
     ``contourComm`` (not in the reference): an object with ``rank``, ``nranks`` and
     ``allreduce(vector) -> vector`` (e.g. ``distributed.ContourReplicas``); contour point k is then
-    solved on rank ``k % nranks`` only."""
+    solved on rank ``k % nranks`` only.
+
+    ``contourPool`` (not in the reference): hand the solves of ALL contour points of an iteration to the backend as one
+    job list, when its ``solveBlock`` takes a shift per right-hand side (``HipVector``: an always-full pool of lock-step
+    solves instead of one contour point at a time).  The sums are formed in the per-point loop's order;
+    ``status["contourPool"]`` then holds, per FEAST iteration, the pool's width, rounds, block products by live
+    operands and the products of every (point, vector) solve.  Other backends keep the per-point loop.
+    ``contourDeal``: how ``contourComm`` deals the work, ``"point"`` (above) or ``"balanced"`` (the pair
+    ``k*nsub + im0`` goes to rank ``(k*nsub + im0) % nranks``: every rank gets the same mix of points)."""
     if convertUnit != "au":
         raise NotImplementedError("unit conversion needs the reference's in-house `util` module")
     cls = type(Y[0])
@@ -149,14 +231,22 @@ def feastDiagonalization(A, Y, nc, quad, eMin, eMax, eConv, maxit, contourEllips
     for it in range(maxit):
         status["outerIter"] = it
         Q = [None] * nsub
+        pairs = _contour_pairs(len(gk), nsub, contourComm, contourDeal)
+        if contourPool and pairs and _takes_shift_per_operand(cls, Y[0]):
+            nodes = [contour_point(eMin, eMax, g, contourEllipseFactor) + (w,) for g, w in zip(gk, wk)]
+            Q, record = _pooled_contour_sums(cls, A, Y[:nsub], pairs, nodes, radius, contourEllipseFactor, status)
+            if record is not None:
+                status.setdefault("contourPool", []).append(record)
+            pairs = []
         for k in range(len(gk)):
-            if contourComm is not None and k % contourComm.nranks != contourComm.rank:
+            mine = [im0 for kk, im0 in pairs if kk == k]
+            if not mine:
                 continue
             status["quadrature"] = k
             theta, z = contour_point(eMin, eMax, gk[k], contourEllipseFactor)
-            terms = _quadrature_terms_block(cls, A, Y[:nsub], z, radius, theta, wk[k], contourEllipseFactor)
-            for im0 in range(nsub):
-                term = terms[im0] if terms is not None else \
+            terms = _quadrature_terms_block(cls, A, [Y[im0] for im0 in mine], z, radius, theta, wk[k], contourEllipseFactor)
+            for j, im0 in enumerate(mine):
+                term = terms[j] if terms is not None else \
                     calculateQuadrature(A, Y[im0], z, radius, theta, wk[k], contourEllipseFactor)
                 Q = updateQ(Q, im0, term, 0 if Q[im0] is None else 1)
         if contourComm is not None:

@@ -428,22 +428,7 @@ def gcrotmk_device_block(ctx, block_matvec, bs, n, rtol=1e-5, atol=0.0, maxiter=
     split = all(hasattr(o, "arnoldi_begin") for o in opss)      # the split (begin / end) step exists for the device ops
     batched = split and ops_factory is None and n <= kind.BATCH_MAX_N and all(o.cols_per_pass in (1, 4) for o in opss)
     while req:
-        # the orthogonalisation steps of all right-hand sides that wait for one: enqueued back to back, collected
-        # afterwards, so that the host work of one (QR insert, bookkeeping) runs under the kernels of the next
-        arn = sorted(i for i, r in req.items() if r[0] == "arn")
-        while arn:
-            batch = arn[:16]
-            if split and all(len(req[i][1]) <= kind.SPLIT_MAX_COLS for i in batch):
-                if not (batched and len(batch) > 1 and all(len(req[i][1]) <= kind.BATCH_MAX_COLS for i in batch) and
-                        kind.arnoldi_begin_batch([opss[i] for i in batch], [(req[i][1], req[i][2]) for i in batch])):
-                    for slot, i in enumerate(batch):
-                        opss[i].arnoldi_begin(req[i][1], req[i][2], slot)
-                for slot, i in enumerate(batch):
-                    advance(i, opss[i].arnoldi_end(len(req[i][1]), slot))
-            else:
-                for i in batch:
-                    advance(i, opss[i].arnoldi_step(req[i][1], req[i][2]))
-            arn = sorted(i for i, r in req.items() if r[0] == "arn")
+        _arnoldi_phase(req, opss, advance, kind, split, batched)
         idx = sorted(req)                                     # everybody left waits for a product
         if not idx:
             break
@@ -451,3 +436,91 @@ def gcrotmk_device_block(ctx, block_matvec, bs, n, rtol=1e-5, atol=0.0, maxiter=
         for i, o in zip(idx, outs):
             advance(i, o)
     return results
+
+
+def _arnoldi_phase(req, opss, advance, kind, split, batched):
+    """The orthogonalisation steps of all solves of a lock-step group that wait for one (``req[i] = ("arn", columns, w)``):
+    enqueued back to back, collected afterwards, so that the host work of one (QR insert, bookkeeping) runs under the
+    kernels of the next.  ``opss[i]``: the vector operations of solve i; ``advance(i, value)`` sends a step's scalars on.
+    Returns when nobody waits for a step any more (everybody left waits for a product)."""
+    arn = sorted(i for i, r in req.items() if r[0] == "arn")
+    while arn:
+        batch = arn[:16]
+        if split and all(len(req[i][1]) <= kind.SPLIT_MAX_COLS for i in batch):
+            if not (batched and len(batch) > 1 and all(len(req[i][1]) <= kind.BATCH_MAX_COLS for i in batch) and
+                    kind.arnoldi_begin_batch([opss[i] for i in batch], [(req[i][1], req[i][2]) for i in batch])):
+                for slot, i in enumerate(batch):
+                    opss[i].arnoldi_begin(req[i][1], req[i][2], slot)
+            for slot, i in enumerate(batch):
+                advance(i, opss[i].arnoldi_end(len(req[i][1]), slot))
+        else:
+            for i in batch:
+                advance(i, opss[i].arnoldi_step(req[i][1], req[i][2]))
+        arn = sorted(i for i, r in req.items() if r[0] == "arn")
+
+
+POOL_MAX_WIDTH = 16          # the library's pinned Arnoldi slots (hipeig.h): at most 16 steps are in flight
+
+
+def gcrotmk_device_pool(ctx, block_matvec, jobs, n, width, rtol=1e-5, atol=0.0, maxiter=1000, m=20, k=None,
+                        complex_pairs=False, cols_per_pass=1, ops_factory=None, pool_stats=None):
+    """An always-full POOL of lock-step solves.  ``jobs``: an ordered list of ``(right-hand side, tag)``; the solves need
+    not share a shift - the solves of all contour points of a FEAST iteration are independent (feast.py:189-200) - so
+    ``block_matvec([v_0, v_1, ...], [tag_0, tag_1, ...]) -> [A_0 v_0, A_1 v_1, ...]`` gets every operand's tag with it.
+    At most ``width`` (<= 16) solves are alive.  A slot whose solve has ended - or whose job needs no product at all, a
+    zero right-hand side - is refilled with the next unstarted job BEFORE the next block product, so the blocks stay
+    full until the job list is empty, where ``gcrotmk_device_block`` thins out towards its slowest solve.  Every solve
+    is the solver above, unchanged: its own spaces, its own recycle pairs, its own stopping test; the pool only decides
+    when its steps run.
+
+    A generator: yields ``(job index, tag, x, info, stats)`` the moment a solve ends, and keeps nothing of that solve
+    afterwards (the caller decides what lives on: 128 solutions are never held at once).  ``pool_stats`` (a dict) is
+    filled with ``width``, ``jobs``, ``rounds`` (block products), ``histogram`` {live operands: block products},
+    ``products`` and ``outer`` (per job, in job order)."""
+    width = int(width)
+    if not 1 <= width <= POOL_MAX_WIDTH:
+        raise ValueError(f"pool width must be 1..{POOL_MAX_WIDTH}, got {width}")
+    jobs = list(jobs)
+    ps = pool_stats if pool_stats is not None else {}
+    ps.update({"width": width, "jobs": len(jobs), "rounds": 0, "histogram": {},
+               "products": [0] * len(jobs), "outer": [0] * len(jobs)})
+    kind = _PairOps if complex_pairs else _Ops
+    gens, opss, req, stats, done = {}, {}, {}, {}, []
+
+    def advance(i, value=None, first=False):
+        try:
+            req[i] = next(gens[i]) if first else gens[i].send(value)
+        except StopIteration as stop:
+            x, info = stop.value
+            ps["products"][i], ps["outer"][i] = stats[i]["matvecs"], stats[i]["outer"]
+            done.append((i, jobs[i][1], x, info, stats.pop(i)))
+            req.pop(i, None)
+            del gens[i], opss[i]                                # the slot is free: nothing of this solve stays alive here
+
+    unstarted = 0
+    while True:
+        while len(gens) < width and unstarted < len(jobs):      # refill: a job that ends at once frees its slot again
+            i, unstarted = unstarted, unstarted + 1
+            if ops_factory is not None:
+                opss[i] = ops_factory()
+            else:
+                opss[i] = _PairOps(ctx, n, cols_per_pass) if complex_pairs else _Ops(ctx, n, cols_per_pass)
+            stats[i] = {"outer": 0, "matvecs": 0}
+            gens[i] = _gcrotmk(opss[i], ctx, jobs[i][0], n, rtol, atol, maxiter, m, k, complex_pairs, None, stats[i])
+            advance(i, first=True)
+        while done:
+            yield done.pop(0)
+        if not req:
+            break
+        live = list(opss.values())
+        split = all(hasattr(o, "arnoldi_begin") for o in live)
+        batched = split and ops_factory is None and n <= kind.BATCH_MAX_N and all(o.cols_per_pass in (1, 4) for o in live)
+        _arnoldi_phase(req, opss, advance, kind, split, batched)
+        if done:
+            continue                                            # a solve ended in its step: refill before the product
+        idx = sorted(req)                                       # everybody alive waits for a product
+        ps["rounds"] += 1
+        ps["histogram"][len(idx)] = ps["histogram"].get(len(idx), 0) + 1
+        outs = block_matvec([req[i][1] for i in idx], [jobs[i][1] for i in idx])
+        for i, o in zip(idx, outs):
+            advance(i, o)

@@ -429,14 +429,28 @@ class HipCsrOperator:
 
     def apply_shifted_pairs(self, z, xs, reverse=False):
         """[sign*(z*x - H x) for x in xs] for complex operands xs = [(re, im) DeviceBuffers, ...]: four operands share one
-        pass over the operator (``hipeig_spmm_shift_pairs``).  Returns new (re, im) buffer pairs."""
-        z = complex(z)
+        pass over the operator (``hipeig_spmm_shift_pairs``).  ``z``: one shift, or a sequence of ``len(xs)`` shifts, one per
+        operand (``hipeig_spmm_shift_pairs_z``: operands of different contour points in one block).  Returns new (re, im)
+        buffer pairs."""
+        per_operand = np.ndim(z) > 0
+        if per_operand:
+            zs = np.asarray(z, dtype=np.complex128).reshape(-1)
+            if len(zs) != len(xs):
+                raise ValueError(f"{len(zs)} shifts for {len(xs)} operands")
+        else:
+            z = complex(z)
         n = self.nrows
         ys = [(self.ctx.alloc(n), self.ctx.alloc(n)) for _ in xs]
         t_xr, k1 = _ptr_table([x[0] for x in xs])
         t_xi, k2 = _ptr_table([x[1] for x in xs])
         t_yr, k3 = _ptr_table([y[0] for y in ys])
         t_yi, k4 = _ptr_table([y[1] for y in ys])
+        if per_operand:
+            zr, zi = np.ascontiguousarray(zs.real), np.ascontiguousarray(zs.imag)
+            DP = C.POINTER(C.c_double)
+            _lib.call("hipeig_spmm_shift_pairs_z", self.ctx.handle, self.handle, len(xs), zr.ctypes.data_as(DP),
+                      zi.ctypes.data_as(DP), -1.0 if reverse else 1.0, t_xr, t_xi, t_yr, t_yi)
+            return ys
         _lib.call("hipeig_spmm_shift_pairs", self.ctx.handle, self.handle, len(xs), z.real, z.imag, -1.0 if reverse else 1.0,
                   t_xr, t_xi, t_yr, t_yi)
         return ys
@@ -491,7 +505,7 @@ class HipVector(AbstractVector):
         lsa.setdefault("linear_tol", 1e-4)
         lsa.setdefault("linear_atol", 1e-4)
         self.options = {"linearSystemArgs": lsa}
-        for extra in ("orthogonalization", "blockSolve", "reduction"):
+        for extra in ("orthogonalization", "blockSolve", "reduction", "contourPoolWidth"):
             if extra in given:
                 self.options[extra] = given[extra]
         self.last_solve_stats = None
@@ -705,7 +719,7 @@ class HipVector(AbstractVector):
     BLOCK_SOLVE_MIN = 3      # fewer right-hand sides are solved one by one (measured at N = 1e6: 2 columns 0.97x, 3: 1.6x, 4: 1.95x, 8: 2.8x)
 
     @staticmethod
-    def solveBlock(H, bs, sigma, x0=None, opType="her", reverseGF=False):
+    def solveBlock(H, bs, sigma, x0=None, opType="her", reverseGF=False, onSolution=None, poolStats=None):
         """``[solve(H, b, sigma) for b in bs]`` with the solves advanced in lock step: one block product
         per MINRES iteration for up to 8 right-hand sides (inexact_Lanczos.py:319-320 calls ``solve``
         once per block vector on the same operator and shift).  Every column runs the recurrences and
@@ -715,8 +729,23 @@ class HipVector(AbstractVector):
         too, for a complex shift (``_solve_complex_block``) and for a real one from ``BLOCK_SOLVE_MIN_GCROT`` right-hand
         sides on, ``BLOCK_SOLVE_MIN_GCROT_LONG`` for vectors longer than one Arnoldi batch (n > 8192;
         ``_solve_real_block``; not with ``options["blockSolve"] = False``).  A context with collectives solves one by one.  Other solvers, an initial guess
-        and fewer right-hand sides take the one-by-one calls."""
+        and fewer right-hand sides take the one-by-one calls.
+
+        ``sigma`` may also be a sequence of ``len(bs)`` shifts, one per right-hand side: the solves of all contour points
+        of a FEAST iteration are independent (feast.py:189-200).  Complex shifts with GCROT, no ``x0``, on one GPU without
+        collectives run as an always-full pool of lock-step solves (``_solve_complex_pool``); anything else one by one,
+        each with its shift.  ``onSolution(i, x_i)``, when given, is called the moment solve i has ended (in the order
+        the solves end) and the returned list then holds ``None`` in place of the solutions handed out, so that a caller
+        who folds each solution into a sum never holds all of them.  ``poolStats``, a dict, receives the pool's record
+        (width, rounds, block products by live operands, products and outer iterations per solve) when the pool ran."""
         bs = list(bs)
+        if np.ndim(sigma) > 0:
+            return HipVector._solve_block_shifts(H, bs, list(sigma), x0, opType, reverseGF, onSolution, poolStats)
+        if onSolution is not None:
+            sols = HipVector.solveBlock(H, bs, sigma, x0, opType, reverseGF)
+            for i, x in enumerate(sols):
+                onSolution(i, x)
+            return [None] * len(sols)
         o = bs[0].options["linearSystemArgs"]
         complex_shift = isinstance(sigma, complex) or np.iscomplexobj(sigma)
 
@@ -867,6 +896,81 @@ class HipVector(AbstractVector):
             res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"]}
             failed = failed or conv != 0
             out.append(res)
+        if failed:
+            raise UserWarning("Warning:: Iterative solver is not converged ")
+        return out
+
+    @staticmethod
+    def _solve_block_shifts(H, bs, shifts, x0, opType, reverseGF, onSolution, poolStats):
+        """``solveBlock`` with one shift per right-hand side."""
+        if len(shifts) != len(bs):
+            raise ValueError(f"{len(shifts)} shifts for {len(bs)} right-hand sides")
+        o = bs[0].options["linearSystemArgs"]
+        if (o["linearSolver"] == "gcrotmk" and x0 is None and isinstance(H, HipCsrOperator)
+                and all(isinstance(z, (complex, np.complexfloating)) for z in shifts)
+                and all(isinstance(b, HipVector) for b in bs)
+                and not bs[0].ctx.direct_only and not bs[0].ctx.collectives):
+            return HipVector._solve_complex_pool(H, bs, [complex(z) for z in shifts], o, reverseGF, onSolution, poolStats)
+        out = []
+        for i, (b, z) in enumerate(zip(bs, shifts)):
+            x = HipVector.solve(H, b, z, x0, opType, reverseGF)
+            if onSolution is not None:
+                onSolution(i, x)
+                x = None
+            out.append(x)
+        return out
+
+    # Device memory one complex GCROT(m, k) solve keeps alive, in complex vectors (16 n bytes each): the iterate and the
+    # residual (2), c outer pairs (2c) and the Arnoldi vectors of a cycle of m + (k - c) steps (m + k - c + 1), largest with
+    # the recycle space full (c = k): 2k + m + 1; plus the new pair (ux, cx), the product just returned and the operand of
+    # a complex scaling while they are being built (4).  SciPy's m = k = 20: 67 vectors, 1072 n bytes.
+    @staticmethod
+    def _pool_vectors_per_solve(m=20, k=20):
+        return 2 + (2 * k + m + 1) + 4
+
+    @staticmethod
+    def _pool_width(ctx, n, options):
+        """Solves the contour pool keeps alive: ``options["contourPoolWidth"]`` when set, else min(16, what nine tenths of
+        the free device memory - the context's recycled buffers of this length included - hold), at least 1."""
+        from .gcrotmk import POOL_MAX_WIDTH
+        forced = options.get("contourPoolWidth")
+        if forced is not None:
+            return max(1, min(POOL_MAX_WIDTH, int(forced)))
+        free = ctx.device_info()["hbm_free"] + 8 * n * len(ctx._pool.get(n, ()))
+        per_solve = 16 * n * HipVector._pool_vectors_per_solve()
+        return max(1, min(POOL_MAX_WIDTH, int(0.9 * free) // per_solve))
+
+    @staticmethod
+    def _solve_complex_pool(H, bs, zs, o, reverseGF, onSolution, poolStats):
+        """The contour solves (z_i*I - H) x_i = b_i, every right-hand side with its own contour point, through an
+        always-full pool of lock-step solves (``gcrotmk_device_pool``): each is the complex GCROT of ``_solve_complex``,
+        unchanged; at most ``_pool_width`` of them are alive, a slot that ends is refilled before the next block product
+        (``hipeig_spmm_shift_pairs_z``: a shift per operand).  Results, ``last_solve_stats`` and the exception on
+        non-convergence, raised once every solve has run, are those of the one-by-one solves.  The pool's own record goes
+        into ``poolStats``."""
+        from .gcrotmk import gcrotmk_device_pool
+        ctx, n = bs[0].ctx, len(bs[0])
+        H.honour_reduction_option(bs[0].options)
+        zero = ctx.alloc(n)                              # the right-hand sides are real and only read: one zero half for all
+        _lib.call("hipeig_vec_fill", ctx.handle, zero.ptr, n, 0.0)
+
+        def block_matvec(vs, tags):
+            return H.apply_shifted_pairs([zs[t] for t in tags], vs, reverse=reverseGF)
+
+        pool = poolStats if poolStats is not None else {}
+        out, failed = [None] * len(bs), False
+        for i, _, x, conv, gstats in gcrotmk_device_pool(
+                ctx, block_matvec, [((b._buf, zero), i) for i, b in enumerate(bs)], n, HipVector._pool_width(ctx, n, bs[0].options),
+                rtol=float(o["linear_tol"]), atol=float(o["linear_atol"]), maxiter=int(o["linearIter"]),
+                complex_pairs=True, cols_per_pass=int(o.get("arnoldiColumnsPerPass", 1)), pool_stats=pool):
+            b = bs[i]
+            res = HipComplexVector(b._new(x[0]), b._new(x[1]))
+            res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"]}
+            failed = failed or conv != 0
+            if onSolution is not None:
+                onSolution(i, res)
+            else:
+                out[i] = res
         if failed:
             raise UserWarning("Warning:: Iterative solver is not converged ")
         return out

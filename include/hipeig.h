@@ -268,6 +268,14 @@ int hipeig_spmm_shift(hipeig_ctx* ctx, hipeig_csr* A, int k, double sigma, doubl
  * share one pass over the operator (an 8-wide block product whose epilogue applies the shift).                        */
 int hipeig_spmm_shift_pairs(hipeig_ctx* ctx, hipeig_csr* A, int npairs, double zr, double zi, double sign,
                             const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim);
+/* The same with one shift PER OPERAND: Y_p = sign*(z_p*X_p - H X_p), zr / zi host arrays of npairs shifts.  The solves of
+ * all contour points of a FEAST iteration are independent (feast.py:189-200), so operands that belong to different points
+ * may share a pass over the operator - the operator sum of a column does not depend on the shift, only the epilogue does.
+ * Chunking (4 or 8 complex operands per pass), kernel choice and the fallbacks (npairs = 1, contexts with collectives:
+ * hipeig_spmv_shift_pair per operand with that operand's shift) are those of hipeig_spmm_shift_pairs; so are the
+ * roundings per element.                                                                                              */
+int hipeig_spmm_shift_pairs_z(hipeig_ctx* ctx, hipeig_csr* A, int npairs, const double* zr, const double* zi, double sign,
+                              const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim);
 /* Kernel choice of the block product / block solve: 0 = automatic, 1 = row-owner CSR (a wavefront per row,
  * 64-byte gathers from wherever the operand block lives), 2 = column-window blocked (operand windows
  * L2-resident, 8 accumulators per row in LDS).  info[0] = variant of the last block launch, [1] = row
