@@ -101,6 +101,77 @@ def mgs(V, w, normalise=True, checkpoints=None):
     return out if checkpoints is not None else out[m]
 
 
+def _dots(Bw, aw):
+    """[dot(b, a) for the rows b of Bw] as a longdouble array (real, already widened operands).  The sum runs along the
+    contiguous axis, so NumPy adds pairwise (a longdouble matrix product would add in sequence)."""
+    if not EXTENDED:
+        return np.array([dot(b, aw) for b in Bw], dtype=LD).reshape(len(Bw))
+    return np.sum(Bw * aw, axis=1) if len(Bw) else np.zeros(0, dtype=LD)
+
+
+def orthonormalize_mgs(Q, x):
+    """The reference's orthogonalize_against_set up to its lindep test (numpyVector.py:132-140) in extended precision: for
+    each row q of Q (shape (m, n), in order)  t1 = x.q, t2 = q.q, x -= q (t1 / t2);  then ip = x.x.
+
+    Returns ``(ip, x_projected, S)`` with the error scale S = ||x_0|| + sum_j |t1_j / t2_j| ||q_j||."""
+    Q = np.asarray(Q, dtype=np.float64)
+    xw = _wide(x).copy()
+    S = nrm2(xw)
+    for q in Q:
+        qw = _wide(q)
+        t1, t2 = dot(xw, qw), dot(qw, qw)
+        coef = t1 / t2
+        xw -= qw * coef
+        S = S + abs(coef) * np.sqrt(t2)
+    return dot(xw, xw), xw, S
+
+
+def orthonormalize_cgs2(Q, x):
+    """Two classical passes  c = Q x; x -= c^T Q  (all coefficients of a pass from the same x, no division by q.q) in
+    extended precision, then ip = x.x.
+
+    Returns ``(ip, x_projected, scales)``; ``scales[p]`` = (||x_p||, sum_j |c_j| ||q_j||, sum_j ||q_j||^2) for pass p, x_p
+    being the vector the pass starts from."""
+    Q = np.asarray(Q, dtype=np.float64)
+    Qw = _wide(Q)
+    xw = _wide(x).copy()
+    qn2 = np.array([dot(q, q) for q in Qw], dtype=LD).reshape(len(Qw))
+    qn = np.sqrt(qn2)
+    scales = []
+    for _ in range(2):
+        c = _dots(Qw, xw)
+        scales.append((nrm2(xw), np.sum(np.abs(c) * qn), np.sum(qn2)))
+        for cj, qw in zip(c, Qw):
+            xw -= cj * qw
+    return dot(xw, xw), xw, scales
+
+
+def gram(A, B):
+    """A B^T and |A| |B|^T for row sets A (ma, n) and B (mb, n) in extended precision: ``(G, Gabs)``."""
+    Aw, Bw = _wide(np.asarray(A, dtype=np.float64)), _wide(np.asarray(B, dtype=np.float64))
+    aA, aB = np.abs(Aw), np.abs(Bw)
+    G = np.empty((len(Aw), len(Bw)), dtype=LD)
+    Gabs = np.empty_like(G)
+    for i in range(len(Aw)):
+        G[i] = _dots(Bw, Aw[i])
+        Gabs[i] = _dots(aB, aA[i])
+    return G, Gabs
+
+
+def combine(V, C):
+    """V^T C and |V|^T |C| for rows V (m, n) and coefficients C (m, k) in extended precision: ``(Y, Yabs)``, shape (n, k) -
+    column c is sum_j C[j, c] V_j."""
+    VT = np.ascontiguousarray(_wide(np.asarray(V, dtype=np.float64)).T)          # (n, m): the sum runs along a row
+    Cw = _wide(np.asarray(C, dtype=np.float64))
+    aVT, aC = np.abs(VT), np.abs(Cw)
+    Y = np.empty((VT.shape[0], Cw.shape[1]), dtype=LD)
+    Yabs = np.empty_like(Y)
+    for c in range(Cw.shape[1]):
+        Y[:, c] = _dots(VT, Cw[:, c])
+        Yabs[:, c] = _dots(aVT, aC[:, c])
+    return Y, Yabs
+
+
 def csr_matvec(rowptr, col, val, x):
     """y = A x for a CSR matrix (any row order of the columns, duplicates summed) in extended precision.
 

@@ -72,7 +72,7 @@ def test_tall_skinny_against_numpy(hip, n, m):
     lc = hip.HipVector.linearCombination(V, c)
     _within(lc.array, Yh @ c, 1e-14 * (np.abs(Yh) @ np.abs(c)) + 1e-300)
     S = hip.HipVector.overlapMatrix(V)
-    _within(S, Yh.T @ Yh, 1e-12 * n)
+    _within(S, Yh.T @ Yh, 1e-13 * (np.abs(Yh).T @ np.abs(Yh)))         # element by element (test_gpu_subspace_kernels.py: <= 400 u)
     assert np.array_equal(S, S.T)
     # block combination (basisTransformation with a matrix)
     Cm = rng.standard_normal((m, 3))
