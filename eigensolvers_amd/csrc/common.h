@@ -139,6 +139,10 @@ struct hipeig_ctx {
   int gather_backend;        // operand exchange: 0 = RCCL (or loopback), 1 = direct peer writes
   int allreduce_backend;     // small (<= 1024 doubles) all-reduces: 0 = RCCL, 1 = the peers' mailboxes (comm_direct.hip)
   int exchange_off;          // measurement aid (hipeig_comm_set_exchange): products place the own slice and skip the exchange
+  // shifted MINRES (minres_shifts.hip): two state records, 3 Lanczos vectors and 4 direction halves per shift
+  double* ms_ws;
+  int64_t ms_ws_doubles;
+  void* h_ms_state;          // pinned copy of one state record
 };
 
 // One blocked copy of the operator (TCOO, TCOO-W, the pair copy of TCOO-W, TCOO-B): the local rows cut into units of

@@ -95,6 +95,8 @@ extern "C" int hipeig_ctx_destroy(hipeig_ctx* c) {
   if (c->mrb_ws) hipFree(c->mrb_ws);
   if (c->d_mrb_state) hipFree(c->d_mrb_state);
   if (c->h_mrb_state) hipHostFree(c->h_mrb_state);
+  if (c->ms_ws) hipFree(c->ms_ws);
+  if (c->h_ms_state) hipHostFree(c->h_ms_state);
   free(c->row_counts);
   hipEventDestroy(c->ev0);
   hipEventDestroy(c->ev1);

@@ -190,6 +190,50 @@ def _pooled_contour_sums(cls, A, Y, pairs, nodes, radius, contourEllipseFactor, 
                "products": list(record["products"]), "outer": list(record["outer"])}
 
 
+def _shares_lanczos(cls, b0):
+    """The vector-major path: the backend solves all contour points of one right-hand side from one Lanczos run
+    (``cls._solve_shifts``) and the vectors ask for it (``linearSolver="minres_shifted"``)."""
+    lsa = getattr(b0, "options", {}).get("linearSystemArgs", {})
+    return lsa.get("linearSolver") == "minres_shifted" and hasattr(cls, "_solve_shifts") and b0.hasExactAddition
+
+
+def _shared_lanczos_sums(cls, A, Y, pairs, nodes, radius, contourEllipseFactor, status):
+    """The filtered vectors of one FEAST iteration vector by vector: ONE ``cls._solve_shifts`` call per subspace vector
+    with all complex contour points this rank holds for it (``pairs`` grouped by ``im0``) - the Krylov space of
+    ``(z_k I - A) x = Y[im0]`` does not depend on ``z_k``.  Real nodes go through ``calculateQuadrature``.  The terms are
+    formed with the arithmetic of ``_quadrature_terms_block`` and added in ascending point order, as
+    ``_pooled_contour_sums`` does.  Returns (Q, record): the products per vector and the iterations per (point, vector)."""
+    nsub = len(Y)
+    Q = [None] * nsub
+    record = {"solves": 0, "products": [], "pairs": [], "iterations": []}
+    for im0 in range(nsub):
+        points = sorted(k for k, i in pairs if i == im0)
+        if not points:
+            continue
+        shifted = [k for k in points if abs(nodes[k][1].imag) >= 1e-15]
+        sols = {}
+        if shifted:
+            xs = cls._solve_shifts(A, Y[im0], [nodes[k][1] for k in shifted])
+            sols = dict(zip(shifted, xs))
+            stats = getattr(Y[im0], "last_solve_stats", None) or {}
+            record["solves"] += 1
+            record["products"].append(stats.get("products"))
+            its = stats.get("iterations") or [None] * len(shifted)
+            for k, n_it in zip(shifted, its):
+                record["pairs"].append([k, im0])
+                record["iterations"].append(n_it)
+        for k in points:
+            theta, z, weight = nodes[k]
+            status["quadrature"] = k
+            if k in sols:
+                phase = contourEllipseFactor * math.cos(theta) + math.sin(theta) * 1j
+                term = cls.real((-0.50 * weight * radius * phase) * sols.pop(k))
+            else:
+                term = calculateQuadrature(A, Y[im0], z, radius, theta, weight, contourEllipseFactor)
+            updateQ(Q, im0, term, 0 if Q[im0] is None else 1)
+    return Q, record
+
+
 def updateQ(Q, im0, Qquad_k, k):
     """Accumulate the k-th quadrature term into the im0-th filtered vector (feast.py:105-121)."""
     if k == 0:
@@ -213,12 +257,20 @@ def feastDiagonalization(A, Y, nc, quad, eMin, eMax, eConv, maxit, contourEllips
     solves instead of one contour point at a time).  The sums are formed in the per-point loop's order;
     ``status["contourPool"]`` then holds, per FEAST iteration, the pool's width, rounds, block products by live
     operands and the products of every (point, vector) solve.  Other backends keep the per-point loop.
+    With ``linearSolver="minres_shifted"`` on a backend that has ``_solve_shifts`` (``HipVector``) the iteration runs vector
+    by vector instead: one shared-Lanczos solve per subspace vector for all of this rank's complex contour points
+    (``shifted_minres.solve_shifts``); ``status["sharedLanczos"]`` holds, per FEAST iteration, the number of such solves,
+    their products and the iterations of every (point, vector).  Not together with ``contourPool``.
     ``contourDeal``: how ``contourComm`` deals the work, ``"point"`` (above) or ``"balanced"`` (the pair
     ``k*nsub + im0`` goes to rank ``(k*nsub + im0) % nranks``: every rank gets the same mix of points)."""
     if convertUnit != "au":
         raise NotImplementedError("unit conversion needs the reference's in-house `util` module")
     cls = type(Y[0])
     nsub = len(Y)
+    shared = _shares_lanczos(cls, Y[0])
+    if shared and contourPool:
+        raise ValueError("contourPool=True pools GCROT solves; linearSolver='minres_shifted' already serves all contour "
+                         "points of a vector from one Lanczos run - use one or the other")
     assert eMax > eMin
     radius = (eMax - eMin) * 0.5
     gk, wk = quadraturePointsWeights(nc, quad, positiveHalf=True)
@@ -232,6 +284,11 @@ def feastDiagonalization(A, Y, nc, quad, eMin, eMax, eConv, maxit, contourEllips
         status["outerIter"] = it
         Q = [None] * nsub
         pairs = _contour_pairs(len(gk), nsub, contourComm, contourDeal)
+        if shared:
+            nodes = [contour_point(eMin, eMax, g, contourEllipseFactor) + (w,) for g, w in zip(gk, wk)]
+            Q, record = _shared_lanczos_sums(cls, A, Y[:nsub], pairs, nodes, radius, contourEllipseFactor, status)
+            status.setdefault("sharedLanczos", []).append(record)
+            pairs = []
         if contourPool and pairs and _takes_shift_per_operand(cls, Y[0]):
             nodes = [contour_point(eMin, eMax, g, contourEllipseFactor) + (w,) for g, w in zip(gk, wk)]
             Q, record = _pooled_contour_sums(cls, A, Y[:nsub], pairs, nodes, radius, contourEllipseFactor, status)

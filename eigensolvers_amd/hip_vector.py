@@ -662,6 +662,11 @@ class HipVector(AbstractVector):
             raise TypeError("HipVector.solve needs a HipCsrOperator (device-resident CSR)")
         if isinstance(b, HipComplexVector):                 # HipVector(complex array) is a HipComplexVector: same entry point
             return HipComplexVector.solve(H, b, sigma, x0, opType, reverseGF)
+        if b.options["linearSystemArgs"]["linearSolver"] == "minres_shifted":
+            # one-shift call of the shared-Lanczos solver (shifted_minres.solve_shifts): a HipComplexVector for a real shift too
+            if x0 is not None:
+                raise NotImplementedError("linearSolver='minres_shifted' starts from x = 0 (no initial guess)")
+            return HipVector._solve_shifts(H, b, [sigma], reverseGF)[0]
         if x0 is not None and not isinstance(x0, (HipVector, HipComplexVector)):
             x0 = HipVector(np.asarray(x0), ctx=b.ctx)      # NumpyVector hands an ndarray on to SciPy; complex arrays become HipComplexVector
         if isinstance(x0, HipComplexVector) and not (isinstance(sigma, complex) or np.iscomplexobj(sigma)):
@@ -715,6 +720,13 @@ class HipVector(AbstractVector):
             # numpyVector.py:175-177: the warning is escalated to an exception
             raise UserWarning("Warning:: Iterative solver is not converged ")
         return res
+
+    @staticmethod
+    def _solve_shifts(H, b, shifts, reverseGF=False):
+        """All of ``shifts`` for one right-hand side from one Lanczos run (``shifted_minres.solve_shifts``); the hook
+        ``feastDiagonalization`` looks for when ``linearSolver`` is ``"minres_shifted"``."""
+        from .shifted_minres import solve_shifts
+        return solve_shifts(H, b, shifts, reverseGF=reverseGF)
 
     BLOCK_SOLVE_MIN = 3      # fewer right-hand sides are solved one by one (measured at N = 1e6: 2 columns 0.97x, 3: 1.6x, 4: 1.95x, 8: 2.8x)
 
@@ -1210,6 +1222,8 @@ class HipComplexVector(AbstractVector):
         if not isinstance(H, HipCsrOperator):
             raise TypeError("HipComplexVector.solve needs a HipCsrOperator (device-resident CSR)")
         o = b.options["linearSystemArgs"]
+        if o["linearSolver"] == "minres_shifted":
+            raise NotImplementedError("linearSolver='minres_shifted' takes a real right-hand side (its Lanczos run is real)")
         if o["linearSolver"] == "pardiso":
             return HipVector._solve_exact_small(H, b, sigma, reverseGF)
         is_complex_shift = isinstance(sigma, complex) or np.iscomplexobj(sigma)

@@ -316,6 +316,18 @@ int hipeig_minres_block(hipeig_ctx* ctx, hipeig_csr* A, double sigma, double sig
                         const double* const* b, double* const* x, double rtol, int maxiter,
                         int* info, double* out_stats);
 
+/* Shifted MINRES: sign*(z_j I - H) x_j = b for nshift (1..8) shifts z_j = zr[j] + i zi[j] - real (zi = 0) or complex -
+ * of one real symmetric operator and one real right-hand side, all from ONE Lanczos run on H: one operator product per
+ * step whatever nshift is.  Each shift keeps a complex rotation recurrence and a three-term direction update, its
+ * residual norm |tau_j| is minimal over the Krylov space, and it stops after the step at which
+ * |tau_j| <= max(atol, rtol*||b||) (SciPy gcrotmk's criterion); its x_j is then left alone.  x_re[j] / x_im[j]: the
+ * halves of x_j (n doubles each, overwritten).  info[j] = 0, or maxiter when shift j was still live there.
+ * out_stats (may be NULL): nshift records of 4 doubles - steps of shift j, |tau_j|, operator products of the run, 0.
+ * One GPU, whole vectors: a context with collectives is refused.                                                  */
+int hipeig_minres_shifts(hipeig_ctx* ctx, hipeig_csr* A, double sign, int nshift, const double* zr,
+                         const double* zi, const double* b, double* const* x_re, double* const* x_im,
+                         double rtol, double atol, int maxiter, int* info, double* out_stats);
+
 /* ---- timing on the library's compute stream (HIP events) --------------------------- */
 int hipeig_timer_start(hipeig_ctx* ctx);
 int hipeig_timer_stop(hipeig_ctx* ctx, float* elapsed_ms);   /* synchronous */

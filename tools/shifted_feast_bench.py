@@ -1,0 +1,174 @@
+#!/usr/bin/env python3
+"""One FEAST iteration (maxit = 1) of config #5's recipe (tools/bench_configs.py: the generated gapped operator, 16
+subspace vectors, 16 Legendre nodes = 8 contour points, window [-0.21, 0.21], inner rtol 1e-5 / atol 1e-7) with the
+``gcrotmk`` path as it stands (one contour point at a time, its 16 solves in lock step) and with
+``linearSolver="minres_shifted"`` (one shared-Lanczos solve per subspace vector for all 8 points), the two modes
+alternating.  One JSON line per run as soon as it is measured; the first line describes the device.
+
+Then the per-phase split of one shared solve (``--phases``, default on): the whole 8-shift solve of the first subspace
+vector timed with ``hipeig_timer_*``, and each of its three kernels alone (HIPEIG_MS_PROBE = 1 sweep / 2 second kernel /
+3 update pass: that kernel launched ``--probe-steps`` times on a state record that does not advance), next to
+``hipeig_spmv`` at the same size and to the update pass's byte model (8 n + 80 n per live shift).
+
+    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted] >> profiles/NN_shifted_feast.jsonl
+
+``--cpu``: instead, the NumPy twin on the host generator's operator (small N): products per shift, no timing claims;
+``--cpu-gcrotmk`` adds SciPy ``gcrotmk``'s product counts for the same points.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import warnings
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def contour(nc):
+    from eigensolvers_amd import feast as pf
+    gk, _ = pf.quadraturePointsWeights(nc, "legendre", positiveHalf=True)
+    return [pf.contour_point(-0.21, 0.21, g)[1] for g in gk]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--m0", type=int, default=16)
+    ap.add_argument("--nc", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--modes", default="gcrotmk,shifted")
+    ap.add_argument("--cols", type=int, default=4, help="arnoldiColumnsPerPass of the gcrotmk mode")
+    ap.add_argument("--phases", type=int, default=1)
+    ap.add_argument("--probe-steps", type=int, default=200)
+    ap.add_argument("--label", default="")
+    ap.add_argument("--cpu", action="store_true")
+    ap.add_argument("--cpu-gcrotmk", action="store_true", help="with --cpu: also count SciPy gcrotmk's products per point")
+    a = ap.parse_args()
+    import numpy as np
+    import scipy.linalg as la
+
+    N, m0 = a.n, a.m0
+    rng = np.random.default_rng(9)
+    if a.cpu:
+        from eigensolvers_amd.generators import gapped_csr_host
+        from eigensolvers_amd.shifted_minres import shifted_minres_host
+        H = gapped_csr_host(N, 32, seed=7)
+        b = rng.standard_normal(N)
+        b /= np.linalg.norm(b)
+        t0 = time.perf_counter()
+        x, its, est, conv = shifted_minres_host(lambda v: H @ v, b, contour(a.nc), 1e-5, 1e-7, 4000)
+        print(json.dumps({"label": a.label, "N": N, "mode": "twin", "seconds": round(time.perf_counter() - t0, 3),
+                          "iterations": [int(i) for i in its], "products": int(its.max()),
+                          "converged": bool(conv.all())}), flush=True)
+        if a.cpu_gcrotmk:                                           # SciPy's gcrotmk, the reference's solver, point by point
+            import scipy.sparse.linalg as spla
+            cnt = []
+            for z in contour(a.nc):
+                c = [0]
+
+                def mv(u, z=z, c=c):
+                    c[0] += 1
+                    return z * u - H @ u
+                op = spla.LinearOperator((N, N), matvec=mv, dtype=complex)
+                spla.gcrotmk(op, b.astype(complex), rtol=1e-5, atol=1e-7, maxiter=4000)
+                cnt.append(c[0])
+            print(json.dumps({"label": a.label, "N": N, "mode": "scipy_gcrotmk", "complex_products_per_point": cnt,
+                              "complex_products": int(sum(cnt))}), flush=True)
+        return
+
+    import eigensolvers_amd as ea
+    lsa = {"gcrotmk": {"linearSolver": "gcrotmk", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7,
+                       "arnoldiColumnsPerPass": a.cols},
+           "shifted": {"linearSolver": "minres_shifted", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7}}
+    Y0 = la.qr(rng.standard_normal((N, m0)), mode="economic")[0]
+    ctx = ea.HipContext.default()
+    print(json.dumps({"device": ctx.device_info()["name"], "N": N, "m0": m0, "contour_points": a.nc // 2, "reps": a.reps,
+                      "label": a.label}), flush=True)
+    H = ea.HipCsrOperator.generate(N, 32, seed=7)
+    counts = {"pairs": 0, "single": 0}
+    inner_pairs, inner_pair = ea.HipCsrOperator.apply_shifted_pairs, ea.HipCsrOperator.apply_shifted_pair
+
+    def counted_pairs(self, z, xs, reverse=False):
+        counts["pairs"] += len(xs)
+        return inner_pairs(self, z, xs, reverse=reverse)
+
+    def counted_pair(self, *args, **kw):
+        counts["single"] += 1
+        return inner_pair(self, *args, **kw)
+    ea.HipCsrOperator.apply_shifted_pairs = counted_pairs
+    ea.HipCsrOperator.apply_shifted_pair = counted_pair
+
+    modes = [m for m in a.modes.split(",") if m]
+    for rep in range(a.reps):
+        for mode in (modes if rep % 2 == 0 else modes[::-1]):
+            counts.update(pairs=0, single=0)
+            Y = [ea.HipVector(Y0[:, i].copy(), {"linearSystemArgs": dict(lsa[mode])}, ctx=ctx) for i in range(m0)]
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                ev, Yf, st = ea.feastDiagonalization(H, Y, a.nc, "legendre", -0.21, 0.21, 1e-4, 1, writeOut=False)
+            ctx.synchronize()
+            dt = time.perf_counter() - t0
+            row = {"label": a.label, "N": N, "mode": mode, "rep": rep, "seconds": round(dt, 3),
+                   "eigenvalues_in_window": int(np.sum((ev >= -0.21) & (ev <= 0.21)))}
+            if mode == "shifted":
+                rec = st["sharedLanczos"][0]
+                row.update({"solves": rec["solves"], "real_products": int(sum(rec["products"])),
+                            "products_per_vector": [int(p) for p in rec["products"]],
+                            "iterations_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk)),
+                                                              int(max(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk))]
+                                                             for kk in range(a.nc // 2)]})
+            else:
+                row.update({"complex_products": counts["pairs"] + counts["single"]})
+            print(json.dumps(row), flush=True)
+
+    if a.phases and "shifted" in modes:
+        zs = contour(a.nc)
+        S = len(zs)
+        b = ea.HipVector(Y0[:, 0].copy(), {"linearSystemArgs": dict(lsa["shifted"])}, ctx=ctx)
+        os.environ.pop("HIPEIG_MS_PROBE", None)
+        ea.solve_shifts(H, b, zs)                                   # warm (workspace, operator copy)
+        ctx.timer_start()
+        ea.solve_shifts(H, b, zs)
+        whole_ms = ctx.timer_stop()
+        st = b.last_solve_stats
+        live_steps = int(sum(st["iterations"]))                    # shift-steps the update passes carried
+        # hipeig_spmv at the same size, the yardstick of the sweep
+        y = ctx.alloc(N)
+        H.apply(b._buf, y)
+        ctx.timer_start()
+        for _ in range(a.probe_steps):
+            H.apply(b._buf, y)
+        spmv_ms = ctx.timer_stop() / a.probe_steps
+        phase = {}
+        bp = ea.HipVector(Y0[:, 0].copy(), {"linearSystemArgs": dict(lsa["shifted"], linearIter=a.probe_steps)}, ctx=ctx)
+        for key, name in (("1", "sweep"), ("2", "second_kernel"), ("3", "update_pass")):
+            os.environ["HIPEIG_MS_PROBE"] = key
+            try:
+                for timed in (False, True):
+                    ctx.timer_start()
+                    try:
+                        ea.solve_shifts(H, bp, zs)
+                    except UserWarning:
+                        pass                                        # a probe run never converges
+                    ms = ctx.timer_stop()
+                phase[name] = ms / a.probe_steps
+            finally:
+                os.environ.pop("HIPEIG_MS_PROBE", None)
+        upd_bytes = (8 + 80 * S) * N                                # all S shifts live in the probe
+        print(json.dumps({"label": a.label, "N": N, "mode": "phases", "shifts": S, "products": st["products"],
+                          "iterations": st["iterations"], "whole_solve_ms": round(whole_ms, 3),
+                          "ms_per_step": round(whole_ms / st["products"], 5),
+                          "mean_live_shifts": round(live_steps / st["products"], 3),
+                          "probe_steps": a.probe_steps,
+                          "sweep_ms": round(phase["sweep"], 5), "second_kernel_ms": round(phase["second_kernel"], 5),
+                          "update_pass_ms_all_live": round(phase["update_pass"], 5),
+                          "hipeig_spmv_ms": round(spmv_ms, 5),
+                          "update_pass_TBps": round(upd_bytes / (phase["update_pass"] * 1e-3) / 1e12, 3),
+                          "second_kernel_TBps": round(24 * N / (phase["second_kernel"] * 1e-3) / 1e12, 3)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
