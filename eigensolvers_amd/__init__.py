@@ -15,6 +15,7 @@ from .hip_vector import HipComplexVector, HipContext, HipCsrOperator, HipVector
 from .checkpoint import latest_checkpoint, load_checkpoint, save_checkpoint
 from .feast import feastDiagonalization
 from .lanczos import inexactLanczosDiagonalization, KrylovSpace, true_residual_norms
+from .lanczos_filter import lanczos_filter, lanczos_filter_host, lanczos_run
 from .shifted_minres import shifted_minres_host, solve_shifts
 from .subspace import (basisTransformation, find_nearest, get_pick_function_close_to_sigma,
                        get_pick_function_maxOvlp)
@@ -23,5 +24,6 @@ __all__ = ["AbstractVector", "LINDEP_DEFAULT_VALUE", "HipContext", "HipCsrOperat
            "feastDiagonalization", "latest_checkpoint", "load_checkpoint", "save_checkpoint",
            "inexactLanczosDiagonalization", "KrylovSpace", "true_residual_norms",
            "basisTransformation", "find_nearest", "get_pick_function_close_to_sigma",
-           "get_pick_function_maxOvlp", "shifted_minres_host", "solve_shifts"]
+           "get_pick_function_maxOvlp", "shifted_minres_host", "solve_shifts",
+           "lanczos_filter", "lanczos_filter_host", "lanczos_run"]
 __version__ = "0.1.0"

@@ -105,6 +105,10 @@ SIGNATURES = {
     "hipeig_dense_solve_small": [_P, _P, _D, _D, _D, _P, _P, _P, _P, _IP],
     "hipeig_minres_block": [_P, _P, _D, _D, C.c_int, _PP, _PP, _D, C.c_int, _IP, _DP],
     "hipeig_minres_shifts": [_P, _P, _D, C.c_int, _DP, _DP, _P, _PP, _PP, _D, _D, C.c_int, _IP, _DP],
+    "hipeig_lanczos_block_scalars": [_P, _P, _D, C.c_int, _PP, C.c_int, _DP, _DP, _D, _D, C.c_int, _DP, _DP, _IP, _DP, _IP,
+                                     _DP],
+    "hipeig_lanczos_block_combine": [_P, _P, C.c_int, _PP, _IP, C.POINTER(_DP), C.POINTER(_DP), C.c_int, C.POINTER(_DP),
+                                     _PP, _DP],
     "hipeig_csr_set_block_variant": [_P, C.c_int],
     "hipeig_csr_block_info": [_P, _I64P],
     "hipeig_timer_start": [_P],

@@ -143,6 +143,10 @@ struct hipeig_ctx {
   double* ms_ws;
   int64_t ms_ws_doubles;
   void* h_ms_state;          // pinned copy of one state record
+  // two-pass Lanczos filter (lanczos_filter.hip): the state record, the scalar tables and 3-4 interleaved blocks
+  double* lf_ws;
+  int64_t lf_ws_doubles;
+  void* h_lf_state;          // pinned copy of the state record
 };
 
 // One blocked copy of the operator (TCOO, TCOO-W, the pair copy of TCOO-W, TCOO-B): the local rows cut into units of

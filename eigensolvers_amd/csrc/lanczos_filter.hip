@@ -1,0 +1,567 @@
+// FEAST's filtered vectors from two Lanczos passes, k <= 8 right-hand sides in lock step on interleaved block products
+// (feast.py:189-200 only ever forms q = sum_k Re(c_k x_k) of the contour solves sign*(z_k I - H) x_k = b; every MINRES
+// iterate x_k lies in the Krylov space of the same real Lanczos basis, so q = sum_i g_i v_i with real g_i that follow
+// from the Lanczos tridiagonal alone).  DESIGN.md section 3.6; the NumPy statement is eigensolvers_amd/lanczos_filter.py.
+//
+// Pass 1 (hipeig_lanczos_block_scalars), three kernels per step, no host round trip, no per-shift vector:
+//   sweep  W = s (H R_k) - (beta_k / beta_{k-1}) R_{k-1}     (block product, fused)  + per-column partials <v_k, w>
+//   KC     W -= (alpha / beta_k) R_k                                                 + per-column partials <w, w>
+//   scalar one workgroup, thread = (column, shift): the rotation recurrence of minres_shifts.hip for up to 32 shifts per
+//          column, live flags, the column's stop, and alpha_k, beta_{k+1} appended to the column's device arrays
+// The Lanczos vectors are kept un-normalised (r_k = beta_k v_k) as in minres_shifts.hip; the per-column sums follow
+// minres_block.hip: every workgroup leaves K partials, the consumer's prologue adds them in a fixed order.  A column that
+// has stopped is masked: its scalars are no longer recorded and its vectors are zeroed (s = 0), never read.
+//
+// Pass 2 (hipeig_lanczos_block_combine), one kernel per step, no reduction: the block sweep's element epilogue does
+//   q[c] += G[r][i][c] v_i ;  r_{i+1} = (H r_i)/beta_i - (beta_i/beta_{i-1}) r_{i-1} - (alpha_i/beta_i) r_i   written over r_{i-1}
+// (v_{i+1} = (H v_i - alpha_i v_i - beta_i v_{i-1}) / beta_{i+1} on pass 1's un-normalised vectors, v_i = r_i / beta_i)
+// from the scalar tables uploaded once; column r stops after its own m_r terms; the last term needs no product.
+#include <math.h>
+#include "spmm_device.h"
+
+int hipeig_block_pick_variant(hipeig_ctx* c, hipeig_csr* A, int K, int for_solve);
+BcooView hipeig_bcoo_view(const hipeig_csr* A, const BlockedLayout& L);
+int hipeig_block_pack(hipeig_ctx* c, int K, int64_t n, int k, const double* const* cols, double* blk);
+int hipeig_block_unpack(hipeig_ctx* c, int K, int64_t n, int k, const double* blk, double* const* cols);
+int hipeig_rowowner_grid(const hipeig_ctx* c, const hipeig_csr* A);
+
+#define LF_MAX_SHIFTS 32
+#define LF_HEAD_DOUBLES 4096                                  // doubles kept for the state record
+
+struct LfCol {
+  double beta1, beta, oldb, s, target;                       // ||b||, beta_k, beta_{k-1}, 1 / beta_k, max(atol, rtol ||b||)
+  int itn, done;                                              // completed steps; the column has stopped
+};
+
+struct LfState {
+  int done, nshift, maxiter, pad;                             // done: every column has stopped
+  LfCol col[BCOO_KMAX];
+  double c1r[BCOO_KMAX][LF_MAX_SHIFTS], c1i[BCOO_KMAX][LF_MAX_SHIFTS], s1[BCOO_KMAX][LF_MAX_SHIFTS];   // rotation k-1
+  double c2r[BCOO_KMAX][LF_MAX_SHIFTS], c2i[BCOO_KMAX][LF_MAX_SHIFTS];                                 // rotation k-2 (its s is not needed here)
+  double taur[BCOO_KMAX][LF_MAX_SHIFTS], taui[BCOO_KMAX][LF_MAX_SHIFTS];
+  int its[BCOO_KMAX][LF_MAX_SHIFTS];
+  int live[BCOO_KMAX][LF_MAX_SHIFTS];
+};
+static_assert(sizeof(LfState) <= LF_HEAD_DOUBLES * sizeof(double), "the state record outgrew its area");
+
+struct LfShifts {
+  double sign;
+  double zr[LF_MAX_SHIFTS], zi[LF_MAX_SHIFTS];
+};
+
+// Block counterpart of LanczosRowEpilogue (minres_shifts.hip): s, c1, use_r1 are those of THIS thread's column.
+template <int K>
+struct LfScalarsEpilogue {
+  double s, c1;
+  int use_r1;
+  const double* __restrict__ rk;
+  const double* __restrict__ rkm1;
+  double* __restrict__ w;
+  __device__ __forceinline__ void elem(int64_t r, int j, double sum, double& acc) const {
+    const int64_t i = r * K + j;
+    const double v = mul_rn(s, rk[i]);
+    double wv = mul_rn(s, sum);
+    if (use_r1) wv = fma(-c1, rkm1[i], wv);
+    w[i] = wv;
+    acc = fma(v, wv, acc);
+  }
+};
+
+// VARIANT 2: window-blocked (TCOO-B) sweep, 1024 threads; VARIANT 1: row-owner CSR sweep, 256 threads.
+template <int VARIANT, int K>
+__global__ void __launch_bounds__(VARIANT == 2 ? BCOO_THREADS : HIPEIG_BLOCK)
+lf_sweep_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                const double* __restrict__ val, int64_t nrows, const LfState* __restrict__ S,
+                const double* __restrict__ rk, const double* __restrict__ rkm1, double* __restrict__ w,
+                double* __restrict__ partials) {
+  __shared__ double red[(VARIANT == 2 ? BCOO_THREADS : HIPEIG_BLOCK) / 64 * K];
+  __shared__ double sh_s[K], sh_c1[K];
+  __shared__ int sh_use[K];
+  extern __shared__ double bcoo_lds[];
+  if (S->done) return;
+  if (threadIdx.x < K) {
+    const LfCol c = S->col[threadIdx.x];
+    const int use = (!c.done && c.itn >= 1);
+    sh_s[threadIdx.x] = c.done ? 0.0 : c.s;
+    sh_c1[threadIdx.x] = use ? c.beta / c.oldb : 0.0;
+    sh_use[threadIdx.x] = use;
+  }
+  __syncthreads();
+  LfScalarsEpilogue<K> epi;
+  const int j = threadIdx.x % K;
+  epi.s = sh_s[j]; epi.c1 = sh_c1[j]; epi.use_r1 = sh_use[j];
+  epi.rk = rk; epi.rkm1 = rkm1; epi.w = w;
+  double acc = 0.0;
+  if (VARIANT == 2) bcoo_wg_sweep<K>(T, rk, epi, acc, bcoo_lds);
+  else csr_rowowner_block_sweep<K>(rowptr, col, val, nrows, rk, epi, acc);
+  const double tot = block_reduce_cols<K>(acc, red);
+  if (threadIdx.x < K) partials[(size_t)blockIdx.x * K + threadIdx.x] = tot;
+}
+
+// Fold (a0, a1) - partials of columns 2(t % (K/2)) and the next - over the workgroup; record in threads 0..K-1.
+template <int K>
+__device__ __forceinline__ void lf_reduce_pairs(double a0, double a1, double* lds, double* __restrict__ out_record) {
+#pragma unroll
+  for (int off = K / 2; off < 64; off <<= 1) {
+    a0 += __shfl_xor(a0, off, 64);
+    a1 += __shfl_xor(a1, off, 64);
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane < K / 2) { lds[wid * K + lane * 2] = a0; lds[wid * K + lane * 2 + 1] = a1; }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    double r = lds[threadIdx.x];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += lds[w * K + threadIdx.x];
+    out_record[threadIdx.x] = r;
+  }
+}
+
+// W -= (alpha / beta_k) R_k per column, and the partials of <w, w>.
+template <int K>
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+lf_kc_kernel(int64_t n, const LfState* __restrict__ S, const double* __restrict__ pA, int nA,
+             const double* __restrict__ rk, double* __restrict__ w, double* __restrict__ partials) {
+  __shared__ double red[HIPEIG_BLOCK / 64 * K];
+  __shared__ double sh_c[K];
+  if (S->done) return;
+  const double alpha = block_sum_partials_cols<K>(pA, nA, red);
+  if (threadIdx.x < K) {
+    const LfCol c = S->col[threadIdx.x];
+    sh_c[threadIdx.x] = c.done ? 0.0 : alpha / c.beta;
+  }
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;           // multiple of K/2: the column pair is fixed per thread
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int j0 = (int)(t0 % (K / 2)) * 2;
+  const double c0 = sh_c[j0], c1 = sh_c[j0 + 1];
+  const double2* r2 = reinterpret_cast<const double2*>(rk);
+  double2* w2 = reinterpret_cast<double2*>(w);
+  double a0 = 0.0, a1 = 0.0;
+  for (int64_t t = t0; t < n * (K / 2); t += stride) {
+    const double2 rv = r2[t];
+    double2 wv = w2[t];
+    wv.x = fma(-c0, rv.x, wv.x); wv.y = fma(-c1, rv.y, wv.y);
+    w2[t] = wv;
+    a0 = fma(wv.x, wv.x, a0); a1 = fma(wv.y, wv.y, a1);
+  }
+  lf_reduce_pairs<K>(a0, a1, red, partials + (size_t)blockIdx.x * K);
+}
+
+// One workgroup of 256: thread (column = t / 32, shift = t % 32) advances that shift's rotation with the expressions of
+// ms_rotate (minres_shifts.hip) - only c, s and tau are needed, no update coefficients - then threads 0..K-1 close their
+// column's step.  probe: timing aid, nothing is stored.
+template <int K>
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+lf_scalar_kernel(LfState* __restrict__ S, LfShifts a, const double* __restrict__ pA, int nA, const double* __restrict__ pC,
+                 int nC, double* __restrict__ alphas, double* __restrict__ betas, int ld, int probe) {
+  __shared__ double red[HIPEIG_BLOCK / 64 * K];
+  __shared__ double sh_alpha[K], sh_betan[K];
+  __shared__ int sh_any[K], sh_done[K];
+  if (S->done) return;
+  const double alpha_t = block_sum_partials_cols<K>(pA, nA, red);
+  const double ww_t = block_sum_partials_cols<K>(pC, nC, red);
+  if (threadIdx.x < K) {
+    sh_alpha[threadIdx.x] = alpha_t;
+    sh_betan[threadIdx.x] = sqrt(ww_t);
+    sh_any[threadIdx.x] = 0;
+  }
+  __syncthreads();
+  const int cj = threadIdx.x / LF_MAX_SHIFTS, j = threadIdx.x % LF_MAX_SHIFTS;
+  if (cj < K && j < S->nshift && !S->col[cj].done && S->live[cj][j]) {
+    const LfCol c = S->col[cj];
+    const double sign = a.sign, alpha = sh_alpha[cj], betan = sh_betan[cj];
+    const double t_up = (c.itn == 0) ? 0.0 : -sign * c.beta;
+    const double tdr = sign * (a.zr[j] - alpha), tdi = sign * a.zi[j];
+    const double t_lo = -sign * betan;
+    const double c1r = S->c1r[cj][j], c1i = S->c1i[cj][j], s1 = S->s1[cj][j];
+    const double tmpr = S->c2r[cj][j] * t_up, tmpi = S->c2i[cj][j] * t_up;
+    const double ddr = -s1 * tmpr + (c1r * tdr - c1i * tdi);  // -s1 tmp + c1 t_d
+    const double ddi = -s1 * tmpi + (c1r * tdi + c1i * tdr);
+    const double nu = hypot(hypot(ddr, ddi), t_lo);
+    const double cr = ddr / nu, ci = ddi / nu, sn = t_lo / nu;
+    const double tr = -sn * S->taur[cj][j], ti = -sn * S->taui[cj][j];
+    const int live = hypot(tr, ti) > c.target;
+    if (!probe) {
+      S->c2r[cj][j] = c1r; S->c2i[cj][j] = c1i;
+      S->c1r[cj][j] = cr; S->c1i[cj][j] = ci; S->s1[cj][j] = sn;
+      S->taur[cj][j] = tr; S->taui[cj][j] = ti;
+      S->its[cj][j] = c.itn + 1;
+      S->live[cj][j] = live;
+    }
+    if (live) atomicOr(&sh_any[cj], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    LfCol c = S->col[threadIdx.x];
+    if (!c.done && !probe) {
+      const double betan = sh_betan[threadIdx.x];
+      alphas[(size_t)threadIdx.x * ld + c.itn] = sh_alpha[threadIdx.x];
+      betas[(size_t)threadIdx.x * (ld + 1) + c.itn + 1] = betan;
+      c.oldb = c.beta; c.beta = betan; c.s = 1.0 / betan;
+      c.itn += 1;
+      c.done = (!sh_any[threadIdx.x] || c.itn >= S->maxiter || !(betan > 0.0)) ? 1 : 0;
+      S->col[threadIdx.x] = c;
+    }
+    sh_done[threadIdx.x] = c.done;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && !probe) {
+    int all = 1;
+    for (int q = 0; q < K; ++q) all &= sh_done[q];
+    S->done = all;
+  }
+}
+
+// ---- pass 2 ------------------------------------------------------------------------------------------------------------
+// Pass 2 repeats pass 1's arithmetic, not only its mathematics: the coefficients G were computed from the alpha, beta of
+// pass 1's vectors, and a Lanczos recurrence amplifies a rounding difference between the two passes' vectors into the
+// rebuilt sums (measured: a single solution rebuilt through a pass 2 on normalised vectors missed its residual bound at
+// rtol 1e-10 by 2.5 %).  So the vectors stay un-normalised here too, and an element goes through the same operations in
+// the same order as in pass 1's sweep epilogue and KC: with the row-owner sweep the vectors are pass 1's bit for bit.
+// Scalars of one step, per column: LF_TAB(K, NC) doubles - s_i = 1 / beta_i [K], beta_i / beta_{i-1} [K] (0 at i = 0),
+// alpha_i / beta_i [K], G[i][K][NC] - formed on the host with the divisions pass 1's kernels make.
+#define LF_TAB(K, NC) ((K) * (3 + (NC)))
+
+template <int K, int NC>
+struct LfCombineEpilogue {
+  double s, c1, c, g0, g1;
+  int acc_on, upd_on;                                        // i < m_r ; i + 1 < m_r
+  const double* __restrict__ rk;
+  double* __restrict__ rkm1;                                 // r_{i-1}, overwritten by r_{i+1} (same element, same thread)
+  double* __restrict__ q0;
+  double* __restrict__ q1;
+  // explicit fused operations with contraction off, as MsUpd::apply: every element rounds alike wherever it is computed
+  __device__ __forceinline__ void elem(int64_t r, int j, double sum, double& acc) const {
+#pragma clang fp contract(off)
+    const int64_t i = r * K + j;
+    const double rv = rk[i];
+    if (acc_on) {
+      const double v = mul_rn(s, rv);
+      q0[i] = fma(g0, v, q0[i]);
+      if (NC == 2) q1[i] = fma(g1, v, q1[i]);
+    }
+    if (upd_on) rkm1[i] = fma(-c, rv, fma(-c1, rkm1[i], mul_rn(s, sum)));
+  }
+};
+
+template <int VARIANT, int K, int NC>
+__global__ void __launch_bounds__(VARIANT == 2 ? BCOO_THREADS : HIPEIG_BLOCK)
+lf_combine_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                  const double* __restrict__ val, int64_t nrows, const double* __restrict__ tab, const int* __restrict__ m,
+                  int step, const double* __restrict__ rk, double* __restrict__ rkm1, double* __restrict__ q0,
+                  double* __restrict__ q1) {
+  __shared__ double sh_tab[LF_TAB(K, NC)];
+  __shared__ int sh_m[K];
+  extern __shared__ double bcoo_lds[];
+  if (threadIdx.x < LF_TAB(K, NC)) sh_tab[threadIdx.x] = tab[threadIdx.x];
+  if (threadIdx.x < K) sh_m[threadIdx.x] = m[threadIdx.x];
+  __syncthreads();
+  LfCombineEpilogue<K, NC> epi;
+  const int j = threadIdx.x % K;
+  epi.s = sh_tab[j]; epi.c1 = sh_tab[K + j]; epi.c = sh_tab[2 * K + j];
+  epi.g0 = sh_tab[3 * K + j * NC]; epi.g1 = (NC == 2) ? sh_tab[3 * K + j * NC + 1] : 0.0;
+  epi.acc_on = step < sh_m[j]; epi.upd_on = step + 1 < sh_m[j];
+  epi.rk = rk; epi.rkm1 = rkm1; epi.q0 = q0; epi.q1 = q1;
+  double acc = 0.0;
+  if (VARIANT == 2) bcoo_wg_sweep<K>(T, rk, epi, acc, bcoo_lds);
+  else csr_rowowner_block_sweep<K>(rowptr, col, val, nrows, rk, epi, acc);
+}
+
+// The last term of the columns that run to the call's last step: q[c] += G[r][i][c] v_i, no product.
+template <int K, int NC>
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+lf_last_term_kernel(int64_t n, const double* __restrict__ tab, const int* __restrict__ m, int step,
+                    const double* __restrict__ rk, double* __restrict__ q0, double* __restrict__ q1) {
+#pragma clang fp contract(off)
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n * K; i += stride) {
+    const int j = (int)(i % K);
+    if (step >= m[j]) continue;
+    const double v = mul_rn(tab[j], rk[i]);
+    q0[i] = fma(tab[3 * K + j * NC], v, q0[i]);
+    if (NC == 2) q1[i] = fma(tab[3 * K + j * NC + 1], v, q1[i]);
+  }
+}
+
+static int lf_env_int(const char* name, int fallback) {
+  const char* e = getenv(name);
+  return (e && atoi(e) > 0) ? atoi(e) : fallback;
+}
+
+static int lf_reserve(hipeig_ctx* c, int64_t need) {
+  if (c->lf_ws_doubles >= need) return 0;
+  if (c->lf_ws) HIPEIG_CHECK(hipFree(c->lf_ws));
+  c->lf_ws = nullptr; c->lf_ws_doubles = 0;
+  HIPEIG_CHECK(hipMalloc((void**)&c->lf_ws, (size_t)need * sizeof(double)));
+  c->lf_ws_doubles = need;
+  return 0;
+}
+
+// interleave width of a block of k columns: as hipeig_spmm (<= 4 take the narrow interleave); HIPEIG_LF_WIDTH = 8 forces the
+// wide one (the order in which a row's terms are added depends on the width, so runs are comparable bit for bit only at
+// the same one)
+static int lf_width(int k) {
+  if (lf_env_int("HIPEIG_LF_WIDTH", 0) == 8) return 8;
+  return k <= 4 ? 4 : 8;
+}
+
+template <int K>
+static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b, int nshift,
+                           const double* zr, const double* zi, double rtol, double atol, int maxiter, double* alphas,
+                           double* betas, int* iterations, double* estimates, int* info, double* out_stats) {
+  const int64_t n = A->nrows;
+  const int64_t nb = ((n * K + 31) & ~(int64_t)31);
+  const int64_t ld = maxiter;
+  const int64_t tabs = ((int64_t)K * (2 * ld + 1) + 31) & ~(int64_t)31;
+  if (lf_reserve(c, LF_HEAD_DOUBLES + tabs + 3 * nb)) return 1;
+  if (!c->h_lf_state) HIPEIG_CHECK(hipHostMalloc((void**)&c->h_lf_state, sizeof(LfState), hipHostMallocDefault));
+  LfState* V = reinterpret_cast<LfState*>(c->lf_ws);
+  double* d_alphas = c->lf_ws + LF_HEAD_DOUBLES;
+  double* d_betas = d_alphas + (int64_t)K * ld;
+  double* R[3] = {c->lf_ws + LF_HEAD_DOUBLES + tabs, c->lf_ws + LF_HEAD_DOUBLES + tabs + nb,
+                  c->lf_ws + LF_HEAD_DOUBLES + tabs + 2 * nb};
+
+  LfState* h = reinterpret_cast<LfState*>(c->h_lf_state);
+  memset(h, 0, sizeof(LfState));
+  h->nshift = nshift; h->maxiter = maxiter;
+  int live = 0;
+  for (int j = 0; j < K; ++j) {
+    double bb = 0.0;
+    if (j < k && hipeig_dot(c, n, b[j], b[j], &bb)) return 1;
+    LfCol& cj = h->col[j];
+    if (bb > 0.0) {
+      cj.beta1 = sqrt(bb); cj.beta = cj.beta1; cj.oldb = 0.0; cj.s = 1.0 / cj.beta1;
+      cj.target = fmax(atol, rtol * cj.beta1);
+      for (int q = 0; q < nshift; ++q) {
+        h->c1r[j][q] = 1.0; h->c2r[j][q] = 1.0; h->taur[j][q] = cj.beta1; h->live[j][q] = 1;
+      }
+      ++live;
+    } else {
+      cj.done = 1;                                            // padding column, or b == 0: q = 0 with no product
+    }
+    if (j < k) betas[(size_t)j * (ld + 1)] = cj.beta1;
+  }
+  h->done = live == 0;
+  if (live == 0) return 0;
+  if (hipeig_block_pack(c, K, n, k, b, R[0])) return 1;
+  HIPEIG_CHECK(hipMemsetAsync(R[1], 0, (size_t)nb * 2 * sizeof(double), c->stream));
+  HIPEIG_CHECK(hipMemcpyAsync(V, h, sizeof(LfState), hipMemcpyHostToDevice, c->stream));
+  if (hipeig_sync_checked(c)) return 4;                       // the pinned record is rewritten by the first copy-back
+
+  const int bv = hipeig_block_pick_variant(c, A, K, 1);
+  if (bv < 0) return 1;
+  const BlockedLayout& L = A->b[layout_slot(K)];
+  const BcooView tview = hipeig_bcoo_view(A, L);
+  if (bv == 2)
+    HIPEIG_CHECK(hipFuncSetAttribute((const void*)lf_sweep_kernel<2, K>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)HIPEIG_BCOO_LDS_MAX));
+  const SweepGrid sg = (bv == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
+  const int gA = sg.wgs, nsweepA = sg.launches;
+  const int nPA = gA * nsweepA;
+  HIPEIG_REQUIRE(nPA <= HIPEIG_MAX_PARTIALS, "too many sweeps for the partial-sum buffer");
+  const int gE = grid_for(n * (K / 2), lf_env_int("HIPEIG_LF_PER_THREAD", 32));
+  double* pA = c->d_partials;
+  double* pC = c->d_partials + (size_t)HIPEIG_MAX_PARTIALS * BCOO_KMAX;
+  HIPEIG_REQUIRE(c->partials_doubles >= (size_t)2 * HIPEIG_MAX_PARTIALS * BCOO_KMAX, "partial-sum workspace too small");
+
+  LfShifts sh;
+  memset(&sh, 0, sizeof(sh));
+  sh.sign = sign;
+  for (int q = 0; q < nshift; ++q) { sh.zr[q] = zr[q]; sh.zi[q] = zi[q]; }
+  // measurement aid (tools/shifted_feast_bench.py): 1 / 2 / 3 launch ONLY the sweep / KC / scalar kernel, `maxiter` times on a
+  // record that does not advance - the time of that phase alone; the results are meaningless
+  const int probe = lf_env_int("HIPEIG_LF_PROBE", 0);
+
+  auto enqueue_sweep = [&](const double* rk, const double* rkm1, double* w) {
+    if (bv == 2) {
+      BcooView tv = tview;
+      for (int sw = 0; sw < nsweepA; ++sw) {
+        tv.unit_begin = sw * gA;
+        hipLaunchKernelGGL((lf_sweep_kernel<2, K>), dim3(gA), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream, tv,
+                           A->d_rowptr, A->d_col, A->d_val, n, (const LfState*)V, rk, rkm1, w, pA + (size_t)sw * gA * K);
+      }
+    } else {
+      hipLaunchKernelGGL((lf_sweep_kernel<1, K>), dim3(gA), dim3(HIPEIG_BLOCK), 0, c->stream, tview, A->d_rowptr, A->d_col,
+                         A->d_val, n, (const LfState*)V, rk, rkm1, w, pA);
+    }
+  };
+
+  // steps between two looks at the state record; kernels launched past the last column's stop return at once
+  const int chunk = lf_env_int("HIPEIG_LF_CHUNK", 32);
+  int steps = 0;
+  while (steps < maxiter) {
+    const int kend = (steps + chunk < maxiter) ? steps + chunk : maxiter;
+    for (; steps < kend; ++steps) {
+      const int kk = probe ? 0 : steps;
+      double* rk = R[kk % 3];
+      double* w = R[(kk + 1) % 3];
+      double* rkm1 = R[(kk + 2) % 3];
+      if (!probe || probe == 1) enqueue_sweep(rk, rkm1, w);
+      if (!probe || probe == 2)
+        hipLaunchKernelGGL(lf_kc_kernel<K>, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, (const LfState*)V,
+                           (const double*)pA, nPA, (const double*)rk, w, pC);
+      if (!probe || probe == 3)
+        hipLaunchKernelGGL(lf_scalar_kernel<K>, dim3(1), dim3(HIPEIG_BLOCK), 0, c->stream, V, sh, (const double*)pA, nPA,
+                           (const double*)pC, gE, d_alphas, d_betas, (int)ld, probe ? 1 : 0);
+    }
+    HIPEIG_CHECK(hipGetLastError());
+    HIPEIG_CHECK(hipMemcpyAsync(h, V, sizeof(LfState), hipMemcpyDeviceToHost, c->stream));
+    if (hipeig_sync_checked(c)) return 4;
+    if (h->done) break;
+  }
+  HIPEIG_REQUIRE(probe || h->done, "the Lanczos pass left the step loop without a stop in every column");
+  int products = 0;
+  for (int j = 0; j < k; ++j) {
+    const int m = h->col[j].itn;
+    if (m > products) products = m;
+    if (m > 0 && !probe) {
+      HIPEIG_CHECK(hipMemcpyAsync(alphas + (size_t)j * ld, d_alphas + (size_t)j * ld, (size_t)m * sizeof(double),
+                                  hipMemcpyDeviceToHost, c->stream));
+      HIPEIG_CHECK(hipMemcpyAsync(betas + (size_t)j * (ld + 1) + 1, d_betas + (size_t)j * (ld + 1) + 1,
+                                  (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    int any = 0;
+    for (int q = 0; q < nshift; ++q) {
+      iterations[(size_t)j * nshift + q] = h->its[j][q];
+      estimates[(size_t)j * nshift + q] = hypot(h->taur[j][q], h->taui[j][q]);
+      any |= h->live[j][q];
+    }
+    info[j] = (probe || any) ? maxiter : 0;
+    if (out_stats) out_stats[1 + j] = m;
+  }
+  if (out_stats) out_stats[0] = probe ? maxiter : products;
+  if (hipeig_sync_checked(c)) return 4;
+  return 0;
+}
+
+extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
+                                            int nshift, const double* zr, const double* zi, double rtol, double atol,
+                                            int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
+                                            int* info, double* out_stats) {
+  HIPEIG_REQUIRE(b && zr && zi && alphas && betas && iterations && estimates && info, "null argument");
+  HIPEIG_REQUIRE(k >= 1 && k <= BCOO_KMAX, "1 to 8 right-hand sides per call");
+  HIPEIG_REQUIRE(nshift >= 1 && nshift <= LF_MAX_SHIFTS, "1 to 32 shifts per run");
+  HIPEIG_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
+  HIPEIG_REQUIRE(maxiter >= 1, "maxiter must be positive");
+  HIPEIG_REQUIRE(!c->collectives, "the Lanczos filter runs on whole vectors (no row partition)");
+  HIPEIG_REQUIRE(A->nrows == A->ncols, "the Lanczos run needs a square operator");
+  for (int j = 0; j < k; ++j) {
+    HIPEIG_REQUIRE(b[j] != nullptr, "null right-hand side");
+    info[j] = 0;
+    betas[(size_t)j * (maxiter + 1)] = 0.0;
+    for (int q = 0; q < nshift; ++q) { iterations[(size_t)j * nshift + q] = 0; estimates[(size_t)j * nshift + q] = 0.0; }
+  }
+  if (out_stats) memset(out_stats, 0, (size_t)(1 + k) * sizeof(double));
+  if (A->nrows == 0) return 0;
+  if (lf_width(k) == 4)
+    return lf_scalars_impl<4>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info, out_stats);
+  return lf_scalars_impl<8>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info, out_stats);
+}
+
+template <int K, int NC>
+static int lf_combine_impl(hipeig_ctx* c, hipeig_csr* A, int k, const double* const* b, const int* m,
+                           const double* const* alphas, const double* const* betas, const double* const* G,
+                           double* const* q, double* out_stats) {
+  const int64_t n = A->nrows;
+  int mmax = 0;
+  for (int j = 0; j < k; ++j) mmax = m[j] > mmax ? m[j] : mmax;
+  if (mmax == 0) {
+    for (int j = 0; j < k * NC; ++j) if (hipeig_vec_fill(c, q[j], n, 0.0)) return 1;
+    return 0;
+  }
+  // device tables: mmax records of LF_TAB doubles, then m[K] as ints
+  const int64_t nb = ((n * K + 31) & ~(int64_t)31);
+  const int64_t tab_d = ((int64_t)mmax * LF_TAB(K, NC) + 2 * K + 31) & ~(int64_t)31;
+  if (lf_reserve(c, LF_HEAD_DOUBLES + tab_d + (2 + NC) * nb)) return 1;
+  double* d_tab = c->lf_ws + LF_HEAD_DOUBLES;
+  int* d_m = reinterpret_cast<int*>(d_tab + (int64_t)mmax * LF_TAB(K, NC));
+  double* Vb[2] = {c->lf_ws + LF_HEAD_DOUBLES + tab_d, c->lf_ws + LF_HEAD_DOUBLES + tab_d + nb};
+  double* Q0 = c->lf_ws + LF_HEAD_DOUBLES + tab_d + 2 * nb;
+  double* Q1 = (NC == 2) ? Q0 + nb : nullptr;
+  double* h_tab = (double*)calloc((size_t)tab_d, sizeof(double));
+  HIPEIG_REQUIRE(h_tab != nullptr, "out of host memory");
+  int* h_m = reinterpret_cast<int*>(h_tab + (int64_t)mmax * LF_TAB(K, NC));
+  for (int j = 0; j < K; ++j) {
+    h_m[j] = j < k ? m[j] : 0;
+    if (j >= k || m[j] == 0) continue;
+    for (int i = 0; i < m[j]; ++i) {
+      double* t = h_tab + (int64_t)i * LF_TAB(K, NC);
+      t[j] = 1.0 / betas[j][i];                              // the divisions of pass 1: LfCol::s, the sweep's c1, KC's c
+      t[K + j] = i ? betas[j][i] / betas[j][i - 1] : 0.0;
+      t[2 * K + j] = alphas[j][i] / betas[j][i];
+      for (int cc = 0; cc < NC; ++cc) t[3 * K + j * NC + cc] = G[j][(size_t)i * NC + cc];
+    }
+  }
+  hipError_t e = hipMemcpyAsync(d_tab, h_tab, (size_t)tab_d * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  free(h_tab);
+  HIPEIG_CHECK(e);
+  if (hipeig_block_pack(c, K, n, k, b, Vb[0])) return 1;
+  const int gS = grid_stream(n * K);
+  HIPEIG_CHECK(hipMemsetAsync(Vb[1], 0, (size_t)nb * (1 + NC) * sizeof(double), c->stream));
+
+  const int bv = hipeig_block_pick_variant(c, A, K, 1);
+  if (bv < 0) return 1;
+  const BlockedLayout& L = A->b[layout_slot(K)];
+  const BcooView tview = hipeig_bcoo_view(A, L);
+  if (bv == 2)
+    HIPEIG_CHECK(hipFuncSetAttribute((const void*)lf_combine_kernel<2, K, NC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)HIPEIG_BCOO_LDS_MAX));
+  const SweepGrid sg = (bv == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
+  for (int i = 0; i + 1 < mmax; ++i) {
+    const double* tab = d_tab + (int64_t)i * LF_TAB(K, NC);
+    const double* rk = Vb[i & 1];
+    double* rkm1 = Vb[(i + 1) & 1];
+    if (bv == 2) {
+      BcooView tv = tview;
+      for (int sw = 0; sw < sg.launches; ++sw) {
+        tv.unit_begin = sw * sg.wgs;
+        hipLaunchKernelGGL((lf_combine_kernel<2, K, NC>), dim3(sg.wgs), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream,
+                           tv, A->d_rowptr, A->d_col, A->d_val, n, tab, (const int*)d_m, i, rk, rkm1, Q0, Q1);
+      }
+    } else {
+      hipLaunchKernelGGL((lf_combine_kernel<1, K, NC>), dim3(sg.wgs), dim3(HIPEIG_BLOCK), 0, c->stream, tview, A->d_rowptr,
+                         A->d_col, A->d_val, n, tab, (const int*)d_m, i, rk, rkm1, Q0, Q1);
+    }
+  }
+  hipLaunchKernelGGL((lf_last_term_kernel<K, NC>), dim3(gS), dim3(HIPEIG_BLOCK), 0, c->stream, n,
+                     (const double*)(d_tab + (int64_t)(mmax - 1) * LF_TAB(K, NC)), (const int*)d_m, mmax - 1,
+                     (const double*)Vb[(mmax - 1) & 1], Q0, Q1);
+  HIPEIG_CHECK(hipGetLastError());
+  if (NC == 1) {
+    if (hipeig_block_unpack(c, K, n, k, Q0, q)) return 1;
+  } else {
+    double* half[BCOO_KMAX];
+    for (int j = 0; j < k; ++j) half[j] = q[2 * j];
+    if (hipeig_block_unpack(c, K, n, k, Q0, half)) return 1;
+    for (int j = 0; j < k; ++j) half[j] = q[2 * j + 1];
+    if (hipeig_block_unpack(c, K, n, k, Q1, half)) return 1;
+  }
+  if (hipeig_sync_checked(c)) return 4;
+  if (out_stats) out_stats[0] = mmax - 1;
+  return 0;
+}
+
+extern "C" int hipeig_lanczos_block_combine(hipeig_ctx* c, hipeig_csr* A, int k, const double* const* b, const int* m,
+                                            const double* const* alphas, const double* const* betas, int nc,
+                                            const double* const* G, double* const* q, double* out_stats) {
+  HIPEIG_REQUIRE(b && m && alphas && betas && G && q, "null argument");
+  HIPEIG_REQUIRE(k >= 1 && k <= BCOO_KMAX, "1 to 8 right-hand sides per call");
+  HIPEIG_REQUIRE(nc == 1 || nc == 2, "one or two combinations per column");
+  HIPEIG_REQUIRE(!c->collectives, "the Lanczos filter runs on whole vectors (no row partition)");
+  HIPEIG_REQUIRE(A->nrows == A->ncols, "the Lanczos run needs a square operator");
+  for (int j = 0; j < k; ++j) {
+    HIPEIG_REQUIRE(m[j] >= 0, "negative number of terms");
+    HIPEIG_REQUIRE(b[j] != nullptr && (m[j] == 0 || (alphas[j] && betas[j] && G[j])), "null column argument");
+    for (int cc = 0; cc < nc; ++cc) HIPEIG_REQUIRE(q[j * nc + cc] != nullptr && q[j * nc + cc] != b[j], "q must not be null or alias b");
+    for (int i = 1; i < m[j]; ++i) HIPEIG_REQUIRE(betas[j][i] > 0.0, "a Lanczos vector past a breakdown was asked for");
+    HIPEIG_REQUIRE(m[j] == 0 || betas[j][0] > 0.0, "terms asked for a zero right-hand side");
+  }
+  if (out_stats) out_stats[0] = 0.0;
+  if (A->nrows == 0) return 0;
+  const int K = lf_width(k);
+  if (K == 4) return nc == 1 ? lf_combine_impl<4, 1>(c, A, k, b, m, alphas, betas, G, q, out_stats)
+                             : lf_combine_impl<4, 2>(c, A, k, b, m, alphas, betas, G, q, out_stats);
+  return nc == 1 ? lf_combine_impl<8, 1>(c, A, k, b, m, alphas, betas, G, q, out_stats)
+                 : lf_combine_impl<8, 2>(c, A, k, b, m, alphas, betas, G, q, out_stats);
+}

@@ -119,15 +119,19 @@ def _quadrature_terms_block(cls, Amat, guesses, z, radius, angle, weight, contou
 def _contour_pairs(npoints, nsub, contourComm=None, contourDeal="point"):
     """The (contour point, subspace vector) pairs this rank solves, in point-major order.  ``"point"``: whole contour
     points round robin (point k on rank ``k % nranks``); ``"balanced"``: pair ``k*nsub + im0`` round robin, so that every
-    rank gets the same mix of points (the points of a contour differ several-fold in the products their solves need)."""
-    if contourDeal not in ("point", "balanced"):
-        raise ValueError(f"unknown contourDeal {contourDeal!r} ('point' or 'balanced')")
+    rank gets the same mix of points (the points of a contour differ several-fold in the products their solves need);
+    ``"vector"``: subspace vector ``im0`` with ALL its contour points on rank ``im0 % nranks`` - for the vector-major
+    solvers, whose Lanczos run per vector every rank would otherwise repeat."""
+    if contourDeal not in ("point", "balanced", "vector"):
+        raise ValueError(f"unknown contourDeal {contourDeal!r} ('point', 'balanced' or 'vector')")
     pairs = [(k, im0) for k in range(npoints) for im0 in range(nsub)]
     if contourComm is None:
         return pairs
     nr, r = contourComm.nranks, contourComm.rank
     if contourDeal == "balanced":
         return [(k, im0) for k, im0 in pairs if (k * nsub + im0) % nr == r]
+    if contourDeal == "vector":
+        return [(k, im0) for k, im0 in pairs if im0 % nr == r]
     return [(k, im0) for k, im0 in pairs if k % nr == r]
 
 
@@ -234,6 +238,53 @@ def _shared_lanczos_sums(cls, A, Y, pairs, nodes, radius, contourEllipseFactor, 
     return Q, record
 
 
+def _filters_lanczos(cls, b0):
+    """The two-pass path: the backend forms ``sum_k Re(c_k x_k)`` for a set of right-hand sides without the solutions
+    (``cls._lanczos_filter``) and the vectors ask for it (``linearSolver="lanczos_filter"``)."""
+    lsa = getattr(b0, "options", {}).get("linearSystemArgs", {})
+    return lsa.get("linearSolver") == "lanczos_filter" and hasattr(cls, "_lanczos_filter") and b0.hasExactAddition
+
+
+def _lanczos_filter_sums(cls, A, Y, pairs, nodes, radius, contourEllipseFactor, status):
+    """The filtered vectors of one FEAST iteration from ``cls._lanczos_filter``: all subspace vectors this rank holds go
+    through ONE call, with this rank's contour points as shifts and ``-0.5 w r phase`` as weights - real nodes included,
+    the recurrence takes a real z as well.  (Vectors that hold different points - ``contourDeal="balanced"`` - take one
+    call per distinct set.)  Returns (Q, record): the backend's runs (groups of right-hand sides that advanced in lock
+    step), the block products of each pass per run, and the steps per (point, vector)."""
+    nsub = len(Y)
+    Q = [None] * nsub
+    record = {"runs": 0, "products_pass1": [], "products_pass2": [], "pairs": [], "steps": []}
+    by_points = {}
+    for im0 in range(nsub):
+        points = tuple(sorted(k for k, i in pairs if i == im0))
+        if points:
+            by_points.setdefault(points, []).append(im0)
+    for points, vecs in by_points.items():
+        shifts, weights = [], []
+        for k in points:
+            theta, z, weight = nodes[k]
+            phase = contourEllipseFactor * math.cos(theta) + math.sin(theta) * 1j
+            shifts.append(z.real if abs(z.imag) < 1e-15 else z)
+            weights.append(-0.50 * weight * radius * phase)
+        status["quadrature"] = points[-1]
+        qs = cls._lanczos_filter(A, [Y[im0] for im0 in vecs], shifts, weights)
+        seen = set()
+        for im0, q in zip(vecs, qs):
+            Q[im0] = q
+            stats = getattr(Y[im0], "last_solve_stats", None) or {}
+            group = stats.get("group", len(seen))
+            if group not in seen:
+                seen.add(group)
+                record["runs"] += 1
+                record["products_pass1"].append(stats.get("products_pass1"))
+                record["products_pass2"].append(stats.get("products_pass2"))
+            its = stats.get("iterations") or [None] * len(points)
+            for k, n_it in zip(points, its):
+                record["pairs"].append([k, im0])
+                record["steps"].append(n_it)
+    return Q, record
+
+
 def updateQ(Q, im0, Qquad_k, k):
     """Accumulate the k-th quadrature term into the im0-th filtered vector (feast.py:105-121)."""
     if k == 0:
@@ -261,13 +312,22 @@ def feastDiagonalization(A, Y, nc, quad, eMin, eMax, eConv, maxit, contourEllips
     by vector instead: one shared-Lanczos solve per subspace vector for all of this rank's complex contour points
     (``shifted_minres.solve_shifts``); ``status["sharedLanczos"]`` holds, per FEAST iteration, the number of such solves,
     their products and the iterations of every (point, vector).  Not together with ``contourPool``.
-    ``contourDeal``: how ``contourComm`` deals the work, ``"point"`` (above) or ``"balanced"`` (the pair
-    ``k*nsub + im0`` goes to rank ``(k*nsub + im0) % nranks``: every rank gets the same mix of points)."""
+    With ``linearSolver="lanczos_filter"`` on a backend that has ``_lanczos_filter`` (``HipVector``) all of this rank's
+    subspace vectors go through ONE call that returns the filtered sums themselves from two Lanczos passes, no solution
+    formed (``lanczos_filter.lanczos_filter``); ``status["lanczosFilter"]`` holds, per FEAST iteration, the runs, the block
+    products of each pass and the steps of every (point, vector).  Not together with ``contourPool`` either.
+    ``contourDeal``: how ``contourComm`` deals the work, ``"point"`` (above), ``"balanced"`` (the pair
+    ``k*nsub + im0`` goes to rank ``(k*nsub + im0) % nranks``: every rank gets the same mix of points) or ``"vector"``
+    (vector ``im0`` with all its points on rank ``im0 % nranks``: no rank repeats another's Lanczos run)."""
     if convertUnit != "au":
         raise NotImplementedError("unit conversion needs the reference's in-house `util` module")
     cls = type(Y[0])
     nsub = len(Y)
     shared = _shares_lanczos(cls, Y[0])
+    filtered = _filters_lanczos(cls, Y[0])
+    if filtered and contourPool:
+        raise ValueError("contourPool=True pools GCROT solves; linearSolver='lanczos_filter' forms the filtered vectors of "
+                         "all contour points from two Lanczos passes - use one or the other")
     if shared and contourPool:
         raise ValueError("contourPool=True pools GCROT solves; linearSolver='minres_shifted' already serves all contour "
                          "points of a vector from one Lanczos run - use one or the other")
@@ -288,6 +348,11 @@ def feastDiagonalization(A, Y, nc, quad, eMin, eMax, eConv, maxit, contourEllips
             nodes = [contour_point(eMin, eMax, g, contourEllipseFactor) + (w,) for g, w in zip(gk, wk)]
             Q, record = _shared_lanczos_sums(cls, A, Y[:nsub], pairs, nodes, radius, contourEllipseFactor, status)
             status.setdefault("sharedLanczos", []).append(record)
+            pairs = []
+        if filtered:
+            nodes = [contour_point(eMin, eMax, g, contourEllipseFactor) + (w,) for g, w in zip(gk, wk)]
+            Q, record = _lanczos_filter_sums(cls, A, Y[:nsub], pairs, nodes, radius, contourEllipseFactor, status)
+            status.setdefault("lanczosFilter", []).append(record)
             pairs = []
         if contourPool and pairs and _takes_shift_per_operand(cls, Y[0]):
             nodes = [contour_point(eMin, eMax, g, contourEllipseFactor) + (w,) for g, w in zip(gk, wk)]

@@ -667,6 +667,9 @@ class HipVector(AbstractVector):
             if x0 is not None:
                 raise NotImplementedError("linearSolver='minres_shifted' starts from x = 0 (no initial guess)")
             return HipVector._solve_shifts(H, b, [sigma], reverseGF)[0]
+        if b.options["linearSystemArgs"]["linearSolver"] == "lanczos_filter":
+            raise NotImplementedError("linearSolver='lanczos_filter' returns FEAST's filtered sums, not solutions: use "
+                                      "feastDiagonalization or lanczos_filter.lanczos_filter")
         if x0 is not None and not isinstance(x0, (HipVector, HipComplexVector)):
             x0 = HipVector(np.asarray(x0), ctx=b.ctx)      # NumpyVector hands an ndarray on to SciPy; complex arrays become HipComplexVector
         if isinstance(x0, HipComplexVector) and not (isinstance(sigma, complex) or np.iscomplexobj(sigma)):
@@ -727,6 +730,14 @@ class HipVector(AbstractVector):
         ``feastDiagonalization`` looks for when ``linearSolver`` is ``"minres_shifted"``."""
         from .shifted_minres import solve_shifts
         return solve_shifts(H, b, shifts, reverseGF=reverseGF)
+
+    @staticmethod
+    def _lanczos_filter(H, B, shifts, weights, reverseGF=False):
+        """``sum_j Re(weights[j] x_j)`` for every right-hand side of ``B`` from two Lanczos passes, no solution formed
+        (``lanczos_filter.lanczos_filter``); the hook ``feastDiagonalization`` looks for when ``linearSolver`` is
+        ``"lanczos_filter"``."""
+        from .lanczos_filter import lanczos_filter
+        return lanczos_filter(H, B, shifts, weights, reverseGF=reverseGF)
 
     BLOCK_SOLVE_MIN = 3      # fewer right-hand sides are solved one by one (measured at N = 1e6: 2 columns 0.97x, 3: 1.6x, 4: 1.95x, 8: 2.8x)
 

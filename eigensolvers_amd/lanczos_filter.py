@@ -1,0 +1,348 @@
+"""FEAST's filtered vector from two Lanczos passes, without any per-shift vector.  DESIGN.md section 3.6.
+
+FEAST never looks at the solutions of its contour solves: it forms ``q = sum_k Re(c_k x_k)`` (feast.py:189-200) with
+``sign*(z_k I - H) x_k = b``.  Every MINRES iterate ``x_k`` lies in the Krylov space of the same real Lanczos basis
+``v_0, v_1, ...`` of ``(H, b)``, so ``q = sum_i g_i v_i`` with real ``g_i = Re(sum_k c_k y_{k,i})``, where ``y_k`` holds
+the coefficients of shift k's iterate in that basis - numbers that follow from the Lanczos tridiagonal alone:
+
+* pass 1 (``lanczos_scalars_host`` / ``hipeig_lanczos_block_scalars``) runs the Lanczos recurrence and the per-shift
+  rotation recurrences of ``shifted_minres_host`` and keeps scalars only: ``alpha_i``, ``beta_i`` and the stop steps;
+* the host turns them into ``g`` (``minres_coefficients``: the QR factors of the shifted tridiagonal, back substitution);
+* pass 2 (``lanczos_combine_host`` / ``hipeig_lanczos_block_combine``) repeats the recurrence from the stored scalars -
+  no dot products - and accumulates ``q += g_i v_i``.
+
+Both passes are an operator product plus a row epilogue, so up to 8 right-hand sides advance in lock step on the
+interleaved block products of ``csrc/spmm_device.h``.  The ``*_host`` functions are the NumPy statement - the
+specification the device code (``csrc/lanczos_filter.hip``) is tested against; ``lanczos_run`` / ``lanczos_filter`` are
+the device entries.  Indices are 0-based: ``betas[0] = ||b||``, step i uses ``v_i``, yields ``alphas[i]`` and
+``betas[i + 1]``, and ``v_{i+1} = (H v_i - alphas[i] v_i - betas[i] v_{i-1}) / betas[i+1]``.
+"""
+import collections
+import ctypes as C
+import math
+
+import numpy as np
+
+__all__ = ["lanczos_scalars_host", "minres_coefficients", "filter_coefficients", "lanczos_combine_host",
+           "lanczos_filter_host", "lanczos_run", "lanczos_filter", "LanczosRun", "LanczosScalars", "MAX_COLUMNS_PER_CALL",
+           "MAX_SHIFTS_PER_RUN"]
+
+MAX_COLUMNS_PER_CALL = 8
+MAX_SHIFTS_PER_RUN = 32
+
+LanczosScalars = collections.namedtuple("LanczosScalars", "alphas betas iterations estimates converged")
+
+
+def _scalars_one(matvec, b, zs, rtol, atol, maxiter, sign):
+    """One column: the loop of ``shifted_minres_host`` - the same scalar expressions in the same order - without its
+    ``d`` and ``x`` vectors."""
+    S = zs.size
+    its = np.zeros(S, dtype=int)
+    beta1 = float(np.linalg.norm(b))
+    if beta1 == 0.0:
+        return LanczosScalars(np.zeros(0), np.zeros(1), its, np.zeros(S), np.ones(S, dtype=bool))
+    target = max(atol, rtol * beta1)
+    c1 = np.ones(S, complex)
+    s1 = np.zeros(S, complex)
+    c2 = np.ones(S, complex)
+    s2 = np.zeros(S, complex)
+    tau = np.full(S, beta1, complex)
+    live = np.ones(S, dtype=bool)
+    alphas, betas = [], [beta1]
+    v_old, v, beta = np.zeros(b.size), b / beta1, 0.0
+    for k in range(1, maxiter + 1):
+        w = matvec(v) - beta * v_old
+        alpha = float(v @ w)
+        w = w - alpha * v
+        beta_new = float(np.linalg.norm(w))
+        alphas.append(alpha)
+        betas.append(beta_new)
+        for j in range(S):
+            if not live[j]:
+                continue
+            t_up, t_d, t_lo = -sign * beta, sign * (zs[j] - alpha), -sign * beta_new
+            tmp = c2[j] * t_up
+            dd = -s1[j] * tmp + c1[j] * t_d
+            nu = math.hypot(abs(dd), abs(t_lo))
+            c, s = dd / nu, t_lo / nu
+            tau[j] = -s * tau[j]
+            c2[j], s2[j], c1[j], s1[j] = c1[j], s1[j], c, s
+            its[j] = k
+            if abs(tau[j]) <= target:
+                live[j] = False
+        if not live.any() or beta_new == 0.0:
+            break
+        v_old, v, beta = v, w / beta_new, beta_new
+    return LanczosScalars(np.array(alphas), np.array(betas), its, np.abs(tau), ~live)
+
+
+def lanczos_scalars_host(matvec, B, shifts, rtol, atol, maxiter, sign=1.0):
+    """Pass 1 for every row of ``B`` (``[K, n]``, real): a list of ``LanczosScalars(alphas[m], betas[m + 1],
+    iterations[S], estimates[S], converged[S])``, m the steps the column ran.  Stop rule, breakdown, ``maxiter`` and a zero
+    right-hand side (m = 0, everything converged at once) as ``shifted_minres_host``; the columns are independent."""
+    B = np.atleast_2d(np.asarray(B, dtype=np.float64))
+    zs = np.asarray(shifts, dtype=complex).reshape(-1)
+    return [_scalars_one(matvec, b, zs, rtol, atol, maxiter, sign) for b in B]
+
+
+def _coefficients_batch(alphas, betas, zs, ms, sign):
+    """``y[R, S, mmax]``: for column r (``alphas[r, :]``, ``betas[r, :]``, padded to ``mmax`` / ``mmax + 1``) and shift s
+    the coefficients of the MINRES iterate at step ``ms[r, s]`` in the Lanczos basis, zero from that step on.  The
+    rotation recurrence of the twin yields column k of R (``nu`` on the diagonal, ``r1``, ``r2`` above it) and entry k
+    of ``Q^H beta_0 e_1`` (``conj(c_k) tau_{k-1}``); neither depends on where a shift stops, so one forward sweep serves
+    all stop steps and the back substitution ``y_k = (t_k - r1_{k+1} y_{k+1} - r2_{k+2} y_{k+2}) / nu_k`` runs in O(m)."""
+    alphas = np.asarray(alphas, dtype=np.float64)
+    betas = np.asarray(betas, dtype=np.float64)
+    ms = np.asarray(ms, dtype=int)
+    R, S = ms.shape
+    mmax = int(ms.max()) if ms.size else 0
+    y = np.zeros((R, S, mmax), complex)
+    if mmax == 0:
+        return y
+    z = np.asarray(zs, dtype=complex).reshape(1, S)
+    nu = np.zeros((mmax, R, S))
+    r1 = np.zeros((mmax, R, S), complex)
+    r2 = np.zeros((mmax, R, S), complex)
+    t = np.zeros((mmax, R, S), complex)
+    c1 = np.ones((R, S), complex)
+    s1 = np.zeros((R, S), complex)
+    c2 = np.ones((R, S), complex)
+    s2 = np.zeros((R, S), complex)
+    tau = np.repeat(betas[:, :1].astype(complex), S, axis=1)
+    with np.errstate(all="ignore"):                      # entries past a column's own steps are never used
+        for k in range(mmax):
+            t_up = (-sign * betas[:, k:k + 1]) if k else np.zeros((R, 1))
+            t_d = sign * (z - alphas[:, k:k + 1])
+            t_lo = -sign * betas[:, k + 1:k + 2]
+            tmp = c2 * t_up
+            r2[k] = np.conj(s2) * t_up
+            r1[k] = np.conj(c1) * tmp + np.conj(s1) * t_d
+            dd = -s1 * tmp + c1 * t_d
+            nu[k] = np.hypot(np.abs(dd), np.abs(t_lo))
+            c, s = dd / nu[k], t_lo / nu[k]
+            t[k] = np.conj(c) * tau
+            tau = -s * tau
+            c2, s2, c1, s1 = c1, s1, c, s
+        y1 = np.zeros((R, S), complex)                   # y_{k+1}, y_{k+2}
+        y2 = np.zeros((R, S), complex)
+        for k in range(mmax - 1, -1, -1):
+            rhs = t[k].copy()
+            if k + 1 < mmax:
+                rhs -= np.where(ms > k + 1, r1[k + 1] * y1, 0.0)
+            if k + 2 < mmax:
+                rhs -= np.where(ms > k + 2, r2[k + 2] * y2, 0.0)
+            yk = np.where(ms > k, rhs / nu[k], 0.0)
+            y[:, :, k] = yk
+            y1, y2 = yk, y1
+    return y
+
+
+def minres_coefficients(alphas, betas, z, m, sign=1.0):
+    """``y`` (complex, length m): the MINRES iterate at step m of ``sign*(z I - H) x = b`` is ``sum_i y[i] v_i``."""
+    m = int(m)
+    a = np.zeros((1, m))
+    bt = np.zeros((1, m + 1))
+    a[0, :] = np.asarray(alphas, dtype=np.float64)[:m]
+    bt[0, :] = np.asarray(betas, dtype=np.float64)[:m + 1]
+    return _coefficients_batch(a, bt, [z], np.array([[m]]), sign)[0, 0]
+
+
+def filter_coefficients(scalars, shifts, weights, sign=1.0):
+    """``G[r]`` (``[m_r, 1]``, real) with ``G[r][i, 0] = Re(sum_j weights[j] y_{j,i})`` for every column of a pass-1 result
+    (a list of records with ``alphas``, ``betas``, ``iterations``), each shift taken at its own stop step."""
+    R = len(scalars)
+    zs = np.asarray(shifts, dtype=complex).reshape(-1)
+    w = np.asarray(weights, dtype=complex).reshape(-1)
+    if w.size != zs.size:
+        raise ValueError("one weight per shift")
+    ms = np.array([[int(i) for i in sc.iterations] for sc in scalars], dtype=int).reshape(R, zs.size)
+    mmax = int(ms.max()) if ms.size else 0
+    a = np.zeros((R, mmax))
+    bt = np.zeros((R, mmax + 1))
+    for r, sc in enumerate(scalars):
+        m = int(ms[r].max()) if zs.size else 0
+        a[r, :m] = np.asarray(sc.alphas)[:m]
+        bt[r, :m + 1] = np.asarray(sc.betas)[:m + 1]
+    y = _coefficients_batch(a, bt, zs, ms, sign)
+    g = np.einsum("j,rji->ri", w, y).real
+    return [np.ascontiguousarray(g[r, :int(ms[r].max()) if zs.size else 0].reshape(-1, 1)) for r in range(R)]
+
+
+def lanczos_combine_host(matvec, B, alphas, betas, G):
+    """Pass 2: for every row r of ``B`` the ``[NC, n]`` array ``sum_i G[r][i, c] v_i`` (``G[r]``: ``[m_r, NC]``), the
+    Lanczos vectors rebuilt from the stored scalars - no dot products; the last term needs no product."""
+    B = np.atleast_2d(np.asarray(B, dtype=np.float64))
+    out = []
+    for r, b in enumerate(B):
+        g = np.asarray(G[r], dtype=np.float64)
+        g = g[:, None] if g.ndim == 1 else g
+        m, nc = g.shape
+        q = np.zeros((nc, b.size))
+        if m:
+            a, bt = np.asarray(alphas[r], dtype=np.float64), np.asarray(betas[r], dtype=np.float64)
+            v_old, v = np.zeros(b.size), b / bt[0]
+            for i in range(m):
+                q += g[i][:, None] * v[None, :]
+                if i + 1 < m:
+                    # pass 1's expressions in pass 1's order: with the same products the vectors repeat bit for bit
+                    w = matvec(v) - (bt[i] if i else 0.0) * v_old
+                    w = w - a[i] * v
+                    v_old, v = v, w / bt[i + 1]
+        out.append(q)
+    return out
+
+
+def lanczos_filter_host(matvec, B, shifts, weights, rtol, atol, maxiter, sign=1.0):
+    """``(q[K, n], scalars)`` with ``q_r = sum_j Re(weights[j] x_{j,r})``, ``x_{j,r}`` the MINRES iterate of
+    ``sign*(z_j I - H) x = B[r]`` at its own stop step; ``scalars`` is pass 1's result.  A shift still live at the step
+    limit raises ``UserWarning``, as the device entry ``lanczos_filter`` does (``lanczos_scalars_host`` only reports)."""
+    B = np.atleast_2d(np.asarray(B, dtype=np.float64))
+    scalars = lanczos_scalars_host(matvec, B, shifts, rtol, atol, maxiter, sign)
+    if not all(np.all(s.converged) for s in scalars):
+        raise UserWarning("Warning:: Iterative solver is not converged ")
+    G = filter_coefficients(scalars, shifts, weights, sign)
+    q = lanczos_combine_host(matvec, B, [s.alphas for s in scalars], [s.betas for s in scalars], G)
+    return np.array([x[0] for x in q]).reshape(len(B), -1), scalars
+
+
+# ---- device ----------------------------------------------------------------------------------------------------------
+class LanczosRun:
+    """Pass 1's result for the columns ``B``: ``scalars[r]`` (a ``LanczosScalars``), ``info[r]`` (0, or the step limit when
+    a shift of column r was still live there), ``groups`` (the column ranges of the calls of <= 8) and
+    ``products_pass1[g]`` (block products of group g).  ``combine(G)`` is pass 2."""
+
+    def __init__(self, H, B, shifts, sign):
+        self.H, self.B, self.shifts, self.sign = H, list(B), list(shifts), sign
+        self.scalars, self.info, self.groups, self.products_pass1, self.products_pass2 = [], [], [], [], []
+
+    @property
+    def converged(self):
+        return all(i == 0 for i in self.info)
+
+    def combine(self, G):
+        """``sum_i G[r][i, c] v_i`` for every column: ``G[r]`` of shape ``[m_r, NC]`` with ``m_r`` at most the steps
+        column r ran.  NC = 1: a list of ``HipVector``; NC = 2: of ``HipComplexVector`` (c = 0 the real half, c = 1 the
+        imaginary one).  ``products_pass2[g]`` then holds the block products of group g: its largest ``m_r`` minus one."""
+        from . import _lib
+        from .hip_vector import HipComplexVector, _ptr_table
+        if len(G) != len(self.B):
+            raise ValueError("one coefficient table per column")
+        tabs = [np.asarray(g, dtype=np.float64) for g in G]
+        tabs = [np.ascontiguousarray(t[:, None] if t.ndim == 1 else t) for t in tabs]
+        nc = {t.shape[1] for t in tabs}
+        if len(nc) != 1 or next(iter(nc)) not in (1, 2):
+            raise ValueError("coefficient tables of one width, NC = 1 or 2")
+        nc = next(iter(nc))
+        ctx, n = self.B[0].ctx, len(self.B[0])
+        out, self.products_pass2 = [], []
+        dp = C.POINTER(C.c_double)
+        for lo, hi in self.groups:
+            k = hi - lo
+            for r in range(lo, hi):
+                if len(tabs[r]) > len(self.scalars[r].alphas):
+                    raise ValueError(f"column {r}: {len(tabs[r])} coefficients but the run took {len(self.scalars[r].alphas)} steps")
+            m = (C.c_int * k)(*[len(tabs[r]) for r in range(lo, hi)])
+            al = [np.ascontiguousarray(self.scalars[r].alphas, dtype=np.float64) for r in range(lo, hi)]
+            be = [np.ascontiguousarray(self.scalars[r].betas, dtype=np.float64) for r in range(lo, hi)]
+            pa = (dp * k)(*[a.ctypes.data_as(dp) for a in al])
+            pb = (dp * k)(*[b.ctypes.data_as(dp) for b in be])
+            pg = (dp * k)(*[tabs[r].ctypes.data_as(dp) for r in range(lo, hi)])
+            bt, keep1 = _ptr_table([b._buf for b in self.B[lo:hi]])
+            bufs = [ctx.alloc(n) for _ in range(k * nc)]
+            qt, keep2 = _ptr_table(bufs)
+            stats = (C.c_double * 2)()
+            _lib.call("hipeig_lanczos_block_combine", ctx.handle, self.H.handle, k, bt, m, pa, pb, nc, pg, qt, stats)
+            self.products_pass2.append(int(stats[0]))
+            for j in range(k):
+                b = self.B[lo + j]
+                if nc == 1:
+                    out.append(b._new(bufs[j]))
+                else:
+                    out.append(HipComplexVector(b._new(bufs[2 * j]), b._new(bufs[2 * j + 1])))
+        return out
+
+
+def _checked_inputs(H, B, what):
+    from .hip_vector import HipComplexVector, HipCsrOperator, HipVector
+    if not isinstance(H, HipCsrOperator):
+        raise TypeError(f"{what} needs a HipCsrOperator (device-resident CSR)")
+    B = list(B)
+    if not B:
+        raise ValueError(f"{what} needs at least one right-hand side")
+    for b in B:
+        if isinstance(b, HipComplexVector) or not isinstance(b, HipVector):
+            raise NotImplementedError("the Lanczos filter takes real HipVector right-hand sides (the Lanczos run is real)")
+    if B[0].ctx.collectives:
+        raise NotImplementedError("the Lanczos filter runs on whole vectors on one GPU: a context with collectives "
+                                  "(row partition, HIPEIG_FORCE_COLLECTIVES) is not supported")
+    return B
+
+
+def lanczos_run(H, B, shifts, reverseGF=False):
+    """Pass 1 on the device (``hipeig_lanczos_block_scalars``) for the real ``HipVector``s ``B`` and up to 32 ``shifts``
+    (real or complex) of ``sign*(z I - H)``, ``sign = -1`` with ``reverseGF``: a ``LanczosRun``.  More than 8 columns are
+    grouped into calls of 8, each in lock step on block products.  Tolerances and the step limit come from
+    ``B[0].options["linearSystemArgs"]`` as in ``solve_shifts``.  Nothing is raised here: ``run.info`` tells."""
+    from . import _lib
+    from .hip_vector import _ptr_table
+    B = _checked_inputs(H, B, "lanczos_run")
+    zs = [complex(z) for z in np.asarray(shifts).reshape(-1)]
+    if not 1 <= len(zs) <= MAX_SHIFTS_PER_RUN:
+        raise ValueError(f"lanczos_run takes 1 to {MAX_SHIFTS_PER_RUN} shifts")
+    ctx = B[0].ctx
+    H.honour_reduction_option(B[0].options)
+    o = B[0].options["linearSystemArgs"]
+    rtol, atol, maxiter = float(o["linear_tol"]), float(o.get("linear_atol", 0.0)), int(o["linearIter"])
+    sign = -1.0 if reverseGF else 1.0
+    run = LanczosRun(H, B, zs, sign)
+    S = len(zs)
+    zr = (C.c_double * S)(*[z.real for z in zs])
+    zi = (C.c_double * S)(*[z.imag for z in zs])
+    for lo in range(0, len(B), MAX_COLUMNS_PER_CALL):
+        hi = min(lo + MAX_COLUMNS_PER_CALL, len(B))
+        k = hi - lo
+        bt, keep = _ptr_table([b._buf for b in B[lo:hi]])
+        alphas = np.zeros((k, maxiter))
+        betas = np.zeros((k, maxiter + 1))
+        its = (C.c_int * (k * S))()
+        est = (C.c_double * (k * S))()
+        info = (C.c_int * k)()
+        stats = (C.c_double * (1 + k))()
+        dp = C.POINTER(C.c_double)
+        _lib.call("hipeig_lanczos_block_scalars", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
+                  alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats)
+        run.groups.append((lo, hi))
+        run.products_pass1.append(int(stats[0]))
+        for j in range(k):
+            m = int(stats[1 + j])
+            it = np.array(its[j * S:(j + 1) * S], dtype=int)
+            run.scalars.append(LanczosScalars(alphas[j, :m].copy(), betas[j, :m + 1].copy(), it,
+                                              np.array(est[j * S:(j + 1) * S]), np.array([info[j] == 0] * S)))
+            run.info.append(int(info[j]))
+    return run
+
+
+def lanczos_filter(H, B, shifts, weights, reverseGF=False):
+    """``[q_r]`` (``HipVector``) with ``q_r = sum_j Re(weights[j] x_{j,r})``, ``x_{j,r}`` the MINRES iterate of
+    ``sign*(z_j I - H) x = B[r]`` at its own stop step - FEAST's filtered vectors with ``weights[j] = -0.5 w_j r phase_j`` -
+    from two Lanczos passes on the device, no solution ever formed.  Every ``b.last_solve_stats`` = ``{"iterations":
+    [per shift], "estimates": [|tau_j|], "products": block products of both passes of b's group, "products_pass1",
+    "products_pass2"}``.  A shift still live at the step limit raises ``UserWarning`` as every other solver does."""
+    B = _checked_inputs(H, B, "lanczos_filter")
+    if len(np.asarray(weights).reshape(-1)) != len(np.asarray(shifts).reshape(-1)):
+        raise ValueError("one weight per shift")
+    run = lanczos_run(H, B, shifts, reverseGF=reverseGF)
+    G = filter_coefficients(run.scalars, run.shifts, weights, run.sign)
+    q = run.combine(G) if run.converged else None
+    for g, (lo, hi) in enumerate(run.groups):
+        p1 = run.products_pass1[g]
+        p2 = run.products_pass2[g] if q is not None else 0
+        for r in range(lo, hi):
+            B[r].last_solve_stats = {"iterations": [int(i) for i in run.scalars[r].iterations],
+                                     "estimates": [float(e) for e in run.scalars[r].estimates],
+                                     "products": p1 + p2, "products_pass1": p1, "products_pass2": p2, "group": g}
+            if q is not None:
+                q[r].last_solve_stats = B[r].last_solve_stats
+    if q is None:
+        raise UserWarning("Warning:: Iterative solver is not converged ")
+    return q

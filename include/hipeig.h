@@ -328,6 +328,26 @@ int hipeig_minres_shifts(hipeig_ctx* ctx, hipeig_csr* A, double sign, int nshift
                          const double* zi, const double* b, double* const* x_re, double* const* x_im,
                          double rtol, double atol, int maxiter, int* info, double* out_stats);
 
+/* FEAST's filtered vectors without any per-shift vector (feast.py:189-200 only forms q = sum_k Re(c_k x_k) of its contour
+ * solves; every x_k lies in the Krylov space of one real Lanczos basis, so q = sum_i g_i v_i with real g_i that follow from
+ * the Lanczos tridiagonal).  PASS 1: the Lanczos recurrence of k (1..8) real right-hand sides in lock step on interleaved
+ * block products, and per (column, shift) the rotation recurrence and stop rule of hipeig_minres_shifts for nshift (1..32)
+ * shifts of sign*(z I - H) - scalars only.  alphas: k rows of maxiter doubles, betas: k rows of maxiter + 1 (betas[0] =
+ * ||b||; step i, 0-based, yields alphas[i] and betas[i + 1]); iterations / estimates: k rows of nshift (stop step, |tau|);
+ * info[j] = 0, or maxiter when a shift of column j was still live there.  out_stats (may be NULL): 1 + k doubles - block
+ * products of the run, then the steps each column ran.  One GPU, whole vectors: a context with collectives is refused.  */
+int hipeig_lanczos_block_scalars(hipeig_ctx* ctx, hipeig_csr* A, double sign, int k, const double* const* b,
+                                 int nshift, const double* zr, const double* zi, double rtol, double atol,
+                                 int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
+                                 int* info, double* out_stats);
+/* PASS 2 of the same (feast.py:189-200): the Lanczos vectors of the k columns rebuilt from pass 1's scalars (alphas[j],
+ * betas[j]: host arrays of m[j] and m[j] + 1 doubles) - no dot products - and q[j*nc + c] = sum_{i < m[j]} G[j][i*nc + c] v_i
+ * for c < nc (1 or 2) accumulated in the block product's epilogue; q: k*nc vectors of n doubles, overwritten.  Column j stops
+ * after its own m[j] terms; the last term needs no product: out_stats[0] (may be NULL) = max_j m[j] - 1 block products. */
+int hipeig_lanczos_block_combine(hipeig_ctx* ctx, hipeig_csr* A, int k, const double* const* b, const int* m,
+                                 const double* const* alphas, const double* const* betas, int nc,
+                                 const double* const* G, double* const* q, double* out_stats);
+
 /* ---- timing on the library's compute stream (HIP events) --------------------------- */
 int hipeig_timer_start(hipeig_ctx* ctx);
 int hipeig_timer_stop(hipeig_ctx* ctx, float* elapsed_ms);   /* synchronous */

@@ -2,17 +2,21 @@
 """One FEAST iteration (maxit = 1) of config #5's recipe (tools/bench_configs.py: the generated gapped operator, 16
 subspace vectors, 16 Legendre nodes = 8 contour points, window [-0.21, 0.21], inner rtol 1e-5 / atol 1e-7) with the
 ``gcrotmk`` path as it stands (one contour point at a time, its 16 solves in lock step) and with
-``linearSolver="minres_shifted"`` (one shared-Lanczos solve per subspace vector for all 8 points), the two modes
-alternating.  One JSON line per run as soon as it is measured; the first line describes the device.
+``linearSolver="minres_shifted"`` (one shared-Lanczos solve per subspace vector for all 8 points) and with
+``linearSolver="lanczos_filter"`` (mode ``filter``: the filtered vectors from two Lanczos passes, 8 vectors in lock step
+on block products, no per-shift vector), the modes alternating.  One JSON line per run as soon as it is measured; the first line describes the device.
 
 Then the per-phase split of one shared solve (``--phases``, default on): the whole 8-shift solve of the first subspace
 vector timed with ``hipeig_timer_*``, and each of its three kernels alone (HIPEIG_MS_PROBE = 1 sweep / 2 second kernel /
 3 update pass: that kernel launched ``--probe-steps`` times on a state record that does not advance), next to
-``hipeig_spmv`` at the same size and to the update pass's byte model (8 n + 80 n per live shift).
+``hipeig_spmv`` at the same size and to the update pass's byte model (8 n + 80 n per live shift).  For the ``filter`` mode:
+one 8-column run with pass 1, the host's coefficients and pass 2 timed apart, pass 1's three kernels alone
+(HIPEIG_LF_PROBE = 1 sweep / 2 second kernel / 3 scalar kernel), and the block sweep's time per column.
 
-    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted] >> profiles/NN_shifted_feast.jsonl
+    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted,filter] >> profiles/NN_shifted_feast.jsonl
 
-``--cpu``: instead, the NumPy twin on the host generator's operator (small N): products per shift, no timing claims;
+``--cpu``: instead, the NumPy twins on the host generator's operator (small N): products per shift of the shared-Lanczos
+solver, and the two-pass filter's products and its difference from the former's sum; no timing claims;
 ``--cpu-gcrotmk`` adds SciPy ``gcrotmk``'s product counts for the same points.
 """
 import argparse
@@ -61,6 +65,20 @@ def main():
         print(json.dumps({"label": a.label, "N": N, "mode": "twin", "seconds": round(time.perf_counter() - t0, 3),
                           "iterations": [int(i) for i in its], "products": int(its.max()),
                           "converged": bool(conv.all())}), flush=True)
+        import importlib
+        import math
+        from eigensolvers_amd import feast as pf
+        lf = importlib.import_module("eigensolvers_amd.lanczos_filter")
+        gk, wk = pf.quadraturePointsWeights(a.nc, "legendre", positiveHalf=True)
+        ws = [-0.5 * w * 0.21 * (math.cos(pf.contour_point(-0.21, 0.21, g)[0]) + 1j * math.sin(pf.contour_point(-0.21, 0.21, g)[0]))
+              for g, w in zip(gk, wk)]
+        t0 = time.perf_counter()
+        q, sc = lf.lanczos_filter_host(lambda v: H @ v, b, contour(a.nc), ws, 1e-5, 1e-7, 4000)
+        ref = sum((w * xj).real for w, xj in zip(ws, x))
+        m = int(sc[0].iterations.max())
+        print(json.dumps({"label": a.label, "N": N, "mode": "filter_twin", "seconds": round(time.perf_counter() - t0, 3),
+                          "iterations": [int(i) for i in sc[0].iterations], "products_pass1": m, "products_pass2": m - 1,
+                          "relative_difference_to_twin_sum": float(np.linalg.norm(q[0] - ref) / np.linalg.norm(ref))}), flush=True)
         if a.cpu_gcrotmk:                                           # SciPy's gcrotmk, the reference's solver, point by point
             import scipy.sparse.linalg as spla
             cnt = []
@@ -80,7 +98,8 @@ def main():
     import eigensolvers_amd as ea
     lsa = {"gcrotmk": {"linearSolver": "gcrotmk", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7,
                        "arnoldiColumnsPerPass": a.cols},
-           "shifted": {"linearSolver": "minres_shifted", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7}}
+           "shifted": {"linearSolver": "minres_shifted", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7},
+           "filter": {"linearSolver": "lanczos_filter", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7}}
     Y0 = la.qr(rng.standard_normal((N, m0)), mode="economic")[0]
     ctx = ea.HipContext.default()
     print(json.dumps({"device": ctx.device_info()["name"], "N": N, "m0": m0, "contour_points": a.nc // 2, "reps": a.reps,
@@ -120,6 +139,13 @@ def main():
                             "iterations_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk)),
                                                               int(max(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk))]
                                                              for kk in range(a.nc // 2)]})
+            elif mode == "filter":
+                rec = st["lanczosFilter"][0]
+                row.update({"runs": rec["runs"], "block_products_pass1": rec["products_pass1"],
+                            "block_products_pass2": rec["products_pass2"],
+                            "steps_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["steps"]) if k == kk)),
+                                                         int(max(i for (k, v), i in zip(rec["pairs"], rec["steps"]) if k == kk))]
+                                                        for kk in range(a.nc // 2)]})
             else:
                 row.update({"complex_products": counts["pairs"] + counts["single"]})
             print(json.dumps(row), flush=True)
@@ -168,6 +194,58 @@ def main():
                           "hipeig_spmv_ms": round(spmv_ms, 5),
                           "update_pass_TBps": round(upd_bytes / (phase["update_pass"] * 1e-3) / 1e12, 3),
                           "second_kernel_TBps": round(24 * N / (phase["second_kernel"] * 1e-3) / 1e12, 3)}), flush=True)
+
+    if a.phases and "filter" in modes:
+        import importlib
+        import math
+        from eigensolvers_amd import feast as pf
+        lf = importlib.import_module("eigensolvers_amd.lanczos_filter")
+        zs = contour(a.nc)
+        gk, wk = pf.quadraturePointsWeights(a.nc, "legendre", positiveHalf=True)
+        ws = [-0.5 * w * 0.21 * (math.cos(pf.contour_point(-0.21, 0.21, g)[0]) + 1j * math.sin(pf.contour_point(-0.21, 0.21, g)[0]))
+              for g, w in zip(gk, wk)]
+        K = min(8, m0)
+        B = [ea.HipVector(Y0[:, i].copy(), {"linearSystemArgs": dict(lsa["filter"])}, ctx=ctx) for i in range(K)]
+        os.environ.pop("HIPEIG_LF_PROBE", None)
+        ea.lanczos_filter(H, B, zs, ws)                             # warm (workspace, operator copy)
+        ctx.timer_start()
+        run = ea.lanczos_run(H, B, zs)
+        pass1_ms = ctx.timer_stop()
+        t0 = time.perf_counter()
+        G = lf.filter_coefficients(run.scalars, zs, ws)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        ctx.timer_start()
+        run.combine(G)
+        pass2_ms = ctx.timer_stop()
+        p1, p2 = run.products_pass1[0], run.products_pass2[0]
+        y = ctx.alloc(N)
+        H.apply(B[0]._buf, y)
+        ctx.timer_start()
+        for _ in range(a.probe_steps):
+            H.apply(B[0]._buf, y)
+        spmv_ms = ctx.timer_stop() / a.probe_steps
+        phase = {}
+        Bp = [ea.HipVector(Y0[:, i].copy(), {"linearSystemArgs": dict(lsa["filter"], linearIter=a.probe_steps)}, ctx=ctx)
+              for i in range(K)]
+        for key, name in (("1", "sweep"), ("2", "second_kernel"), ("3", "scalar_kernel")):
+            os.environ["HIPEIG_LF_PROBE"] = key
+            try:
+                for timed in (False, True):
+                    ctx.timer_start()
+                    ea.lanczos_run(H, Bp, zs)                       # a probe run never converges; lanczos_run only reports
+                    ms = ctx.timer_stop()
+                phase[name] = ms / a.probe_steps
+            finally:
+                os.environ.pop("HIPEIG_LF_PROBE", None)
+        print(json.dumps({"label": a.label, "N": N, "mode": "filter_phases", "columns": K, "shifts": len(zs),
+                          "block_variant": H.block_info()["variant"],
+                          "block_products_pass1": p1, "block_products_pass2": p2,
+                          "pass1_ms": round(pass1_ms, 3), "host_coefficients_ms": round(host_ms, 3), "pass2_ms": round(pass2_ms, 3),
+                          "pass1_ms_per_step": round(pass1_ms / p1, 5), "pass2_ms_per_step": round(pass2_ms / max(p2, 1), 5),
+                          "probe_steps": a.probe_steps, "sweep_ms": round(phase["sweep"], 5),
+                          "second_kernel_ms": round(phase["second_kernel"], 5), "scalar_kernel_ms": round(phase["scalar_kernel"], 5),
+                          "sweep_ms_per_column": round(phase["sweep"] / K, 5), "hipeig_spmv_ms": round(spmv_ms, 5),
+                          "second_kernel_TBps": round(24 * N * K / (phase["second_kernel"] * 1e-3) / 1e12, 3)}), flush=True)
 
 
 if __name__ == "__main__":
