@@ -147,7 +147,18 @@ struct hipeig_ctx {
   double* lf_ws;
   int64_t lf_ws_doubles;
   void* h_lf_state;          // pinned copy of the state record
+  // segments of released kept bases (hipeig_lanczos_basis_release), handed out again at the same size: a FEAST run asks
+  // for the same sizes every iteration and hipFree synchronises the device.  Emptied when an allocation fails.
+  struct LfPoolEntry* lf_pool;
+  int lf_pool_n, lf_pool_cap;
+  int64_t lf_pool_bytes;
 };
+
+struct LfPoolEntry {
+  double* p;
+  size_t bytes;
+};
+void hipeig_lf_pool_clear(hipeig_ctx* c);   // lanczos_filter.hip: hipFree every pooled segment
 
 // One blocked copy of the operator (TCOO, TCOO-W, the pair copy of TCOO-W, TCOO-B): the local rows cut into units of
 // `rw` rows, the columns into windows of 2^wbits; the non-zeros of (unit, window) tile t, stored as

@@ -99,6 +99,8 @@ extern "C" int hipeig_ctx_destroy(hipeig_ctx* c) {
   if (c->h_ms_state) hipHostFree(c->h_ms_state);
   if (c->lf_ws) hipFree(c->lf_ws);
   if (c->h_lf_state) hipHostFree(c->h_lf_state);
+  hipeig_lf_pool_clear(c);
+  free(c->lf_pool);
   free(c->row_counts);
   hipEventDestroy(c->ev0);
   hipEventDestroy(c->ev1);

@@ -16,6 +16,9 @@
 //   q[c] += G[r][i][c] v_i ;  r_{i+1} = (H r_i)/beta_i - (beta_i/beta_{i-1}) r_{i-1} - (alpha_i/beta_i) r_i   written over r_{i-1}
 // (v_{i+1} = (H v_i - alpha_i v_i - beta_i v_{i-1}) / beta_{i+1} on pass 1's un-normalised vectors, v_i = r_i / beta_i)
 // from the scalar tables uploaded once; column r stops after its own m_r terms; the last term needs no product.
+//
+// Keep mode (hipeig_lanczos_block_scalars_keep): pass 1 leaves every r_k in a slot of a basis in device memory instead of
+// a ring of three, and pass 2 (hipeig_lanczos_basis_combine) is one stream over the slots - see "kept basis" below.
 #include <math.h>
 #include "spmm_device.h"
 
@@ -305,10 +308,96 @@ static int lf_width(int k) {
   return k <= 4 ? 4 : 8;
 }
 
+// ---- kept basis --------------------------------------------------------------------------------------------------------
+// Pass 1 writes every r_k = beta_k v_k once anyway.  In keep mode step k's w goes to slot k + 1 of the basis instead of the
+// oldest ring buffer (the sweep reads slots k and k - 1, KC updates slot k + 1 in place), so the vectors of the run stay
+// in HBM at no extra byte of traffic, and pass 2 becomes one stream over them (lf_basis_combine_kernel) - pass 1's vectors
+// themselves, whichever sweep produced them.  Slots are carved from segments of seg_slots slots, allocated while the run
+// advances; a fresh slot is fully written by the sweep (every row, padding columns as 0) before anything reads it.
+struct hipeig_lanczos_basis {
+  int K, k, seg_slots, nseg, seg_cap;
+  int64_t n, nb, nrows;                                       // nb: doubles per slot; nrows: the operator's
+  size_t seg_bytes;
+  int steps[BCOO_KMAX];                                       // vectors kept per column: v_0 .. v_{steps - 1}
+  double** seg;
+};
+
+void hipeig_lf_pool_clear(hipeig_ctx* c) {
+  for (int i = 0; i < c->lf_pool_n; ++i) (void)hipFree(c->lf_pool[i].p);
+  c->lf_pool_n = 0; c->lf_pool_bytes = 0;
+}
+
+// A segment of `bytes`: a pooled one of that size, else a fresh allocation.  nullptr when the device has no room even
+// after the pool was emptied - an expected outcome (the caller falls back to the ring), so the error state is cleared.
+static double* lf_pool_take(hipeig_ctx* c, size_t bytes) {
+  for (int i = 0; i < c->lf_pool_n; ++i)
+    if (c->lf_pool[i].bytes == bytes) {
+      double* p = c->lf_pool[i].p;
+      c->lf_pool[i] = c->lf_pool[--c->lf_pool_n];
+      c->lf_pool_bytes -= (int64_t)bytes;
+      return p;
+    }
+  double* p = nullptr;
+  if (hipMalloc((void**)&p, bytes) == hipSuccess) return p;
+  (void)hipGetLastError();
+  if (c->lf_pool_n == 0) return nullptr;
+  hipeig_lf_pool_clear(c);
+  if (hipMalloc((void**)&p, bytes) == hipSuccess) return p;
+  (void)hipGetLastError();
+  return nullptr;
+}
+
+static void lf_pool_give(hipeig_ctx* c, double* p, size_t bytes) {
+  if (c->lf_pool_n == c->lf_pool_cap) {
+    const int cap = c->lf_pool_cap ? 2 * c->lf_pool_cap : 64;
+    LfPoolEntry* grown = (LfPoolEntry*)realloc(c->lf_pool, (size_t)cap * sizeof(LfPoolEntry));
+    if (!grown) { (void)hipFree(p); return; }
+    c->lf_pool = grown; c->lf_pool_cap = cap;
+  }
+  c->lf_pool[c->lf_pool_n].p = p; c->lf_pool[c->lf_pool_n].bytes = bytes;
+  ++c->lf_pool_n;
+  c->lf_pool_bytes += (int64_t)bytes;
+}
+
+static inline double* lf_slot(const hipeig_lanczos_basis* B, int i) {
+  return B->seg[i / B->seg_slots] + (int64_t)(i % B->seg_slots) * B->nb;
+}
+
+// One more segment, unless it would exceed the byte budget or the device has no room: 0 = added.
+static int lf_basis_grow(hipeig_ctx* c, hipeig_lanczos_basis* B, int64_t budget) {
+  if ((int64_t)(B->nseg + 1) * (int64_t)B->seg_bytes > budget) return 1;
+  if (B->nseg == B->seg_cap) {
+    const int cap = B->seg_cap ? 2 * B->seg_cap : 16;
+    double** grown = (double**)realloc(B->seg, (size_t)cap * sizeof(double*));
+    if (!grown) return 1;
+    B->seg = grown; B->seg_cap = cap;
+  }
+  double* p = lf_pool_take(c, B->seg_bytes);
+  if (!p) return 1;
+  B->seg[B->nseg++] = p;
+  return 0;
+}
+
+// Hand the segments from index `from` on back to the context (work enqueued on them is ordered before their next use:
+// one stream).
+static void lf_basis_trim(hipeig_ctx* c, hipeig_lanczos_basis* B, int from) {
+  while (B->nseg > from) lf_pool_give(c, B->seg[--B->nseg], B->seg_bytes);
+}
+
+static void lf_basis_free(hipeig_ctx* c, hipeig_lanczos_basis* B) {
+  if (!B) return;
+  lf_basis_trim(c, B, 0);
+  free(B->seg);
+  free(B);
+}
+
+// keep != nullptr: keep mode with `budget` bytes for the segments; *keep receives the basis, or nullptr when it was not kept
+// (budget or device memory ran out: the run went on in the ring of three, same kernels, same operands, same scalars).
 template <int K>
 static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b, int nshift,
                            const double* zr, const double* zi, double rtol, double atol, int maxiter, double* alphas,
-                           double* betas, int* iterations, double* estimates, int* info, double* out_stats) {
+                           double* betas, int* iterations, double* estimates, int* info, double* out_stats,
+                           int64_t budget, hipeig_lanczos_basis** keep) {
   const int64_t n = A->nrows;
   const int64_t nb = ((n * K + 31) & ~(int64_t)31);
   const int64_t ld = maxiter;
@@ -343,8 +432,30 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   }
   h->done = live == 0;
   if (live == 0) return 0;
-  if (hipeig_block_pack(c, K, n, k, b, R[0])) return 1;
-  HIPEIG_CHECK(hipMemsetAsync(R[1], 0, (size_t)nb * 2 * sizeof(double), c->stream));
+  // measurement aid (tools/shifted_feast_bench.py): 1 / 2 / 3 launch ONLY the sweep / KC / scalar kernel, `maxiter` times on a
+  // record that does not advance - the time of that phase alone; the results are meaningless
+  const int probe = lf_env_int("HIPEIG_LF_PROBE", 0);
+  // steps between two looks at the state record; kernels launched past the last column's stop return at once
+  const int chunk = lf_env_int("HIPEIG_LF_CHUNK", 32);
+  struct Guard {
+    hipeig_ctx* c; hipeig_lanczos_basis* B;
+    ~Guard() { lf_basis_free(c, B); }
+  } kept{c, nullptr};
+  if (keep && !probe) {
+    hipeig_lanczos_basis* B = (hipeig_lanczos_basis*)calloc(1, sizeof(hipeig_lanczos_basis));
+    HIPEIG_REQUIRE(B != nullptr, "out of host memory");
+    B->K = K; B->k = k; B->n = n; B->nb = nb; B->nrows = A->nrows;
+    B->seg_slots = lf_env_int("HIPEIG_LF_SEGMENT", 32);       // slots per segment
+    B->seg_bytes = (size_t)B->seg_slots * (size_t)nb * sizeof(double);
+    kept.B = B;
+    if (lf_basis_grow(c, B, budget)) { lf_basis_free(c, B); kept.B = nullptr; }
+  }
+  if (kept.B) {
+    if (hipeig_block_pack(c, K, n, k, b, lf_slot(kept.B, 0))) return 1;
+  } else {
+    if (hipeig_block_pack(c, K, n, k, b, R[0])) return 1;
+    HIPEIG_CHECK(hipMemsetAsync(R[1], 0, (size_t)nb * 2 * sizeof(double), c->stream));
+  }
   HIPEIG_CHECK(hipMemcpyAsync(V, h, sizeof(LfState), hipMemcpyHostToDevice, c->stream));
   if (hipeig_sync_checked(c)) return 4;                       // the pinned record is rewritten by the first copy-back
 
@@ -368,9 +479,6 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   memset(&sh, 0, sizeof(sh));
   sh.sign = sign;
   for (int q = 0; q < nshift; ++q) { sh.zr[q] = zr[q]; sh.zi[q] = zi[q]; }
-  // measurement aid (tools/shifted_feast_bench.py): 1 / 2 / 3 launch ONLY the sweep / KC / scalar kernel, `maxiter` times on a
-  // record that does not advance - the time of that phase alone; the results are meaningless
-  const int probe = lf_env_int("HIPEIG_LF_PROBE", 0);
 
   auto enqueue_sweep = [&](const double* rk, const double* rkm1, double* w) {
     if (bv == 2) {
@@ -386,16 +494,25 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
     }
   };
 
-  // steps between two looks at the state record; kernels launched past the last column's stop return at once
-  const int chunk = lf_env_int("HIPEIG_LF_CHUNK", 32);
   int steps = 0;
   while (steps < maxiter) {
     const int kend = (steps + chunk < maxiter) ? steps + chunk : maxiter;
+    // the segments this chunk writes (slots up to kend) before it is enqueued; when the budget or the device says no, the
+    // two live vectors move to the ring and the run goes on as plain pass 1
+    while (kept.B && kept.B->nseg * kept.B->seg_slots <= kend)
+      if (lf_basis_grow(c, kept.B, budget)) {
+        HIPEIG_CHECK(hipMemcpyAsync(R[steps % 3], lf_slot(kept.B, steps), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (steps)
+          HIPEIG_CHECK(hipMemcpyAsync(R[(steps + 2) % 3], lf_slot(kept.B, steps - 1), (size_t)nb * sizeof(double),
+                                      hipMemcpyDeviceToDevice, c->stream));
+        lf_basis_free(c, kept.B);
+        kept.B = nullptr;
+      }
     for (; steps < kend; ++steps) {
       const int kk = probe ? 0 : steps;
-      double* rk = R[kk % 3];
-      double* w = R[(kk + 1) % 3];
-      double* rkm1 = R[(kk + 2) % 3];
+      double* rk = kept.B ? lf_slot(kept.B, kk) : R[kk % 3];
+      double* w = kept.B ? lf_slot(kept.B, kk + 1) : R[(kk + 1) % 3];
+      double* rkm1 = kept.B ? lf_slot(kept.B, kk ? kk - 1 : 0) : R[(kk + 2) % 3];   // step 0 reads no r_{-1}
       if (!probe || probe == 1) enqueue_sweep(rk, rkm1, w);
       if (!probe || probe == 2)
         hipLaunchKernelGGL(lf_kc_kernel<K>, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, (const LfState*)V,
@@ -428,16 +545,22 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
     }
     info[j] = (probe || any) ? maxiter : 0;
     if (out_stats) out_stats[1 + j] = m;
+    if (kept.B) kept.B->steps[j] = m;
   }
   if (out_stats) out_stats[0] = probe ? maxiter : products;
   if (hipeig_sync_checked(c)) return 4;
+  if (kept.B) {                                               // memory follows the steps taken: slots 0 .. products - 1
+    lf_basis_trim(c, kept.B, (products + kept.B->seg_slots - 1) / kept.B->seg_slots);
+    *keep = kept.B;
+    kept.B = nullptr;
+  }
   return 0;
 }
 
-extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
-                                            int nshift, const double* zr, const double* zi, double rtol, double atol,
-                                            int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
-                                            int* info, double* out_stats) {
+static int lf_scalars_entry(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b, int nshift,
+                            const double* zr, const double* zi, double rtol, double atol, int maxiter, double* alphas,
+                            double* betas, int* iterations, double* estimates, int* info, double* out_stats, int64_t budget,
+                            hipeig_lanczos_basis** keep) {
   HIPEIG_REQUIRE(b && zr && zi && alphas && betas && iterations && estimates && info, "null argument");
   HIPEIG_REQUIRE(k >= 1 && k <= BCOO_KMAX, "1 to 8 right-hand sides per call");
   HIPEIG_REQUIRE(nshift >= 1 && nshift <= LF_MAX_SHIFTS, "1 to 32 shifts per run");
@@ -454,8 +577,30 @@ extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double
   if (out_stats) memset(out_stats, 0, (size_t)(1 + k) * sizeof(double));
   if (A->nrows == 0) return 0;
   if (lf_width(k) == 4)
-    return lf_scalars_impl<4>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info, out_stats);
-  return lf_scalars_impl<8>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info, out_stats);
+    return lf_scalars_impl<4>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
+                              out_stats, budget, keep);
+  return lf_scalars_impl<8>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
+                            out_stats, budget, keep);
+}
+
+extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
+                                            int nshift, const double* zr, const double* zi, double rtol, double atol,
+                                            int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
+                                            int* info, double* out_stats) {
+  return lf_scalars_entry(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
+                          out_stats, 0, nullptr);
+}
+
+extern "C" int hipeig_lanczos_block_scalars_keep(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
+                                                 int nshift, const double* zr, const double* zi, double rtol, double atol,
+                                                 int maxiter, double* alphas, double* betas, int* iterations,
+                                                 double* estimates, int* info, double* out_stats, int64_t basis_bytes,
+                                                 hipeig_lanczos_basis** basis) {
+  HIPEIG_REQUIRE(basis != nullptr, "null argument");
+  *basis = nullptr;
+  HIPEIG_REQUIRE(basis_bytes >= 0, "negative byte budget");
+  return lf_scalars_entry(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
+                          out_stats, basis_bytes, basis);
 }
 
 template <int K, int NC>
@@ -564,4 +709,165 @@ extern "C" int hipeig_lanczos_block_combine(hipeig_ctx* c, hipeig_csr* A, int k,
                              : lf_combine_impl<4, 2>(c, A, k, b, m, alphas, betas, G, q, out_stats);
   return nc == 1 ? lf_combine_impl<8, 1>(c, A, k, b, m, alphas, betas, G, q, out_stats)
                  : lf_combine_impl<8, 2>(c, A, k, b, m, alphas, betas, G, q, out_stats);
+}
+
+// ---- pass 2 from a kept basis ------------------------------------------------------------------------------------------
+// q[c] = sum_{i < m_j} G[j][i][c] v_i, v_i = r_i / beta_i, over the stored vectors: one stream, no product.  A thread owns
+// one double2 of the interleaved [row][K] layout - a fixed pair of columns, as lf_kc_kernel - keeps its 2 NC accumulators
+// in registers and takes the slots in ascending order, LF_BC_UNROLL independent 16-byte loads in flight; q is written
+// once.  Every element goes through the operations of LfCombineEpilogue::elem / lf_last_term_kernel - v = mul_rn(1/beta_i,
+// r_i), q = fma(G, v, q), contraction off - so with the row-owner sweep the result equals the product pass bit for bit.
+// The coefficients differ per column (not wave-uniform): they and the slot pointers are staged through LDS, LF_BC_STEPS
+// steps at a time.  Table of one step: 1 / beta_i [K], G[i][K][NC], zero from a column's m_j on (those terms are skipped).
+#define LF_BC_STEPS 32
+#define LF_BC_UNROLL 4
+#define LF_BC_TAB(K, NC) ((K) * (1 + (NC)))
+
+// a slot pointer comes out of LDS, so the compiler no longer knows that it points to global memory: say so, or the
+// loads become flat ones
+typedef double lf_double2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(1))) lf_double2* lf_global_double2;
+
+template <int K, int NC>
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+lf_basis_combine_kernel(int64_t n2, int mmax, const double* __restrict__ tab, const double* const* __restrict__ slots,
+                        const int* __restrict__ m, double* __restrict__ Q, int64_t nb) {
+#pragma clang fp contract(off)
+  constexpr int TW = LF_BC_TAB(K, NC);
+  __shared__ double sh_tab[LF_BC_STEPS * TW];
+  __shared__ const double* sh_slot[LF_BC_STEPS];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;           // multiple of K/2: the column pair is fixed per thread
+  const int j0 = (int)(threadIdx.x % (K / 2)) * 2;                  // blockDim.x is one too
+  const int m0 = m[j0], m1 = m[j0 + 1];
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n2; base += stride) {   // uniform per workgroup (barriers inside)
+    const int64_t t = base + threadIdx.x;
+    const bool on = t < n2;
+    double a0[NC], a1[NC];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) { a0[cc] = 0.0; a1[cc] = 0.0; }
+    for (int i0 = 0; i0 < mmax; i0 += LF_BC_STEPS) {
+      const int ns = (mmax - i0 < LF_BC_STEPS) ? mmax - i0 : LF_BC_STEPS;
+      __syncthreads();
+      for (int x = threadIdx.x; x < ns * TW; x += blockDim.x) sh_tab[x] = tab[(int64_t)i0 * TW + x];
+      if ((int)threadIdx.x < ns) sh_slot[threadIdx.x] = slots[i0 + threadIdx.x];
+      __syncthreads();
+      if (!on) continue;
+      auto term = [&](int ii, const lf_double2 rv) {
+        const double* tb = sh_tab + ii * TW;
+        const double v0 = mul_rn(tb[j0], rv.x), v1 = mul_rn(tb[j0 + 1], rv.y);
+        if (i0 + ii < m0) {
+#pragma unroll
+          for (int cc = 0; cc < NC; ++cc) a0[cc] = fma(tb[K + j0 * NC + cc], v0, a0[cc]);
+        }
+        if (i0 + ii < m1) {
+#pragma unroll
+          for (int cc = 0; cc < NC; ++cc) a1[cc] = fma(tb[K + (j0 + 1) * NC + cc], v1, a1[cc]);
+        }
+      };
+      int ii = 0;
+      for (; ii + LF_BC_UNROLL <= ns; ii += LF_BC_UNROLL) {
+        lf_double2 rv[LF_BC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < LF_BC_UNROLL; ++u) rv[u] = ((lf_global_double2)sh_slot[ii + u])[t];
+#pragma unroll
+        for (int u = 0; u < LF_BC_UNROLL; ++u) term(ii + u, rv[u]);
+      }
+      for (; ii < ns; ++ii) term(ii, ((lf_global_double2)sh_slot[ii])[t]);
+    }
+    if (on) {
+#pragma unroll
+      for (int cc = 0; cc < NC; ++cc) reinterpret_cast<double2*>(Q + (int64_t)cc * nb)[t] = make_double2(a0[cc], a1[cc]);
+    }
+  }
+}
+
+template <int K, int NC>
+static int lf_basis_combine_impl(hipeig_ctx* c, const hipeig_lanczos_basis* B, int k, const int* m,
+                                 const double* const* betas, const double* const* G, double* const* q) {
+  const int64_t n = B->n, nb = B->nb;
+  int mmax = 0;
+  for (int j = 0; j < k; ++j) mmax = m[j] > mmax ? m[j] : mmax;
+  if (mmax == 0) {
+    for (int j = 0; j < k * NC; ++j) if (hipeig_vec_fill(c, q[j], n, 0.0)) return 1;
+    return 0;
+  }
+  // device tables: mmax records of LF_BC_TAB doubles, mmax slot pointers, then m[K] as ints
+  constexpr int TW = LF_BC_TAB(K, NC);
+  const int64_t tab_d = ((int64_t)mmax * (TW + 1) + K + 31) & ~(int64_t)31;
+  if (lf_reserve(c, LF_HEAD_DOUBLES + tab_d + NC * nb)) return 1;
+  double* d_tab = c->lf_ws + LF_HEAD_DOUBLES;
+  const double** d_slots = reinterpret_cast<const double**>(d_tab + (int64_t)mmax * TW);
+  int* d_m = reinterpret_cast<int*>(d_tab + (int64_t)mmax * (TW + 1));
+  double* Q = c->lf_ws + LF_HEAD_DOUBLES + tab_d;
+  static_assert(sizeof(double*) == sizeof(double), "slot pointers are stored in the table's doubles");
+  double* h_tab = (double*)calloc((size_t)tab_d, sizeof(double));
+  HIPEIG_REQUIRE(h_tab != nullptr, "out of host memory");
+  const double** h_slots = reinterpret_cast<const double**>(h_tab + (int64_t)mmax * TW);
+  int* h_m = reinterpret_cast<int*>(h_tab + (int64_t)mmax * (TW + 1));
+  for (int i = 0; i < mmax; ++i) h_slots[i] = lf_slot(B, i);
+  for (int j = 0; j < K; ++j) {
+    h_m[j] = j < k ? m[j] : 0;
+    for (int i = 0; i < h_m[j]; ++i) {
+      double* t = h_tab + (int64_t)i * TW;
+      t[j] = 1.0 / betas[j][i];                              // LfCol::s, as lf_combine_impl
+      for (int cc = 0; cc < NC; ++cc) t[K + j * NC + cc] = G[j][(size_t)i * NC + cc];
+    }
+  }
+  hipError_t e = hipMemcpyAsync(d_tab, h_tab, (size_t)tab_d * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  free(h_tab);
+  HIPEIG_CHECK(e);
+  const int64_t n2 = n * (K / 2);
+  hipLaunchKernelGGL((lf_basis_combine_kernel<K, NC>), dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream, n2, mmax,
+                     (const double*)d_tab, (const double* const*)d_slots, (const int*)d_m, Q, nb);
+  HIPEIG_CHECK(hipGetLastError());
+  for (int cc = 0; cc < NC; ++cc) {
+    double* part[BCOO_KMAX];
+    for (int j = 0; j < k; ++j) part[j] = q[j * NC + cc];
+    if (hipeig_block_unpack(c, K, n, k, Q + (int64_t)cc * nb, part)) return 1;
+  }
+  if (hipeig_sync_checked(c)) return 4;
+  return 0;
+}
+
+extern "C" int hipeig_lanczos_basis_combine(hipeig_ctx* c, const hipeig_lanczos_basis* B, int k, const int* m,
+                                            const double* const* betas, int nc, const double* const* G, double* const* q) {
+  HIPEIG_REQUIRE(B && m && betas && G && q, "null argument");
+  HIPEIG_REQUIRE(k == B->k, "the basis was kept for another number of columns");
+  HIPEIG_REQUIRE(nc == 1 || nc == 2 || nc == 4 || nc == 8, "1, 2, 4 or 8 combinations per column");
+  HIPEIG_REQUIRE(!c->collectives, "the Lanczos filter runs on whole vectors (no row partition)");
+  for (int j = 0; j < k; ++j) {
+    HIPEIG_REQUIRE(m[j] >= 0 && m[j] <= B->steps[j], "more terms than the vectors kept for the column");
+    HIPEIG_REQUIRE(m[j] == 0 || (betas[j] && G[j]), "null column argument");
+    for (int cc = 0; cc < nc; ++cc) HIPEIG_REQUIRE(q[j * nc + cc] != nullptr, "q must not be null");
+    for (int i = 0; i < m[j]; ++i) HIPEIG_REQUIRE(betas[j][i] > 0.0, "a Lanczos vector past a breakdown was asked for");
+  }
+  if (B->n == 0) return 0;
+#define LF_BC_CASE(KK, NN) if (B->K == KK && nc == NN) return lf_basis_combine_impl<KK, NN>(c, B, k, m, betas, G, q);
+  LF_BC_CASE(4, 1) LF_BC_CASE(4, 2) LF_BC_CASE(4, 4) LF_BC_CASE(4, 8)
+  LF_BC_CASE(8, 1) LF_BC_CASE(8, 2) LF_BC_CASE(8, 4) LF_BC_CASE(8, 8)
+#undef LF_BC_CASE
+  HIPEIG_REQUIRE(false, "unknown interleave width");
+}
+
+extern "C" int hipeig_lanczos_basis_info(hipeig_ctx* c, const hipeig_lanczos_basis* B, int64_t info[8]) {
+  HIPEIG_REQUIRE(info != nullptr, "null argument");
+  memset(info, 0, 8 * sizeof(int64_t));
+  info[5] = c->lf_pool_bytes;
+  if (!B) return 0;
+  int top = 0;
+  for (int j = 0; j < B->k; ++j) top = B->steps[j] > top ? B->steps[j] : top;
+  info[0] = top;
+  info[1] = (int64_t)B->nseg * (int64_t)B->seg_bytes;
+  info[2] = B->K;
+  info[3] = B->n;
+  info[4] = B->k;
+  info[6] = B->nseg;
+  info[7] = B->seg_slots;
+  return 0;
+}
+
+extern "C" int hipeig_lanczos_basis_release(hipeig_ctx* c, hipeig_lanczos_basis* B) {
+  lf_basis_free(c, B);
+  return 0;
 }

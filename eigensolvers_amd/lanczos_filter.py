@@ -11,6 +11,9 @@ the coefficients of shift k's iterate in that basis - numbers that follow from t
 * pass 2 (``lanczos_combine_host`` / ``hipeig_lanczos_block_combine``) repeats the recurrence from the stored scalars -
   no dot products - and accumulates ``q += g_i v_i``.
 
+With ``keepBasis`` / ``basis="keep"`` pass 1 keeps its vectors in device memory (``hipeig_lanczos_block_scalars_keep``) and
+pass 2 is one stream over them (``hipeig_lanczos_basis_combine``): no second set of products, any number of combinations.
+
 Both passes are an operator product plus a row epilogue, so up to 8 right-hand sides advance in lock step on the
 interleaved block products of ``csrc/spmm_device.h``.  The ``*_host`` functions are the NumPy statement - the
 specification the device code (``csrc/lanczos_filter.hip``) is tested against; ``lanczos_run`` / ``lanczos_filter`` are
@@ -20,15 +23,78 @@ the device entries.  Indices are 0-based: ``betas[0] = ||b||``, step i uses ``v_
 import collections
 import ctypes as C
 import math
+import weakref
 
 import numpy as np
 
 __all__ = ["lanczos_scalars_host", "minres_coefficients", "filter_coefficients", "lanczos_combine_host",
            "lanczos_filter_host", "lanczos_run", "lanczos_filter", "LanczosRun", "LanczosScalars", "MAX_COLUMNS_PER_CALL",
-           "MAX_SHIFTS_PER_RUN"]
+           "MAX_SHIFTS_PER_RUN", "basis_budget", "split_combinations", "BASIS_MODES"]
 
 MAX_COLUMNS_PER_CALL = 8
 MAX_SHIFTS_PER_RUN = 32
+BASIS_MODES = ("recompute", "keep")
+BASIS_SAFETY = 0.9                       # share of the memory in sight a kept basis may take, as the contour pool's
+BASIS_COMBINE_WIDTHS = (8, 4, 2, 1)      # combinations per column one hipeig_lanczos_basis_combine call takes
+
+
+def basis_budget(hbm_free, reusable, override=None, held=0):
+    """Bytes the next group's kept basis may take.  Without ``override``: nine tenths of the free device memory plus the
+    bytes of released bases the context hands out again (memory this run's earlier groups hold is no longer free, so it
+    is counted already).  With ``override`` (``basisBytes``): that many bytes for the whole run, less the bytes ``held``
+    by its earlier groups.  Never negative."""
+    if override is not None:
+        if int(override) < 0:
+            raise ValueError("basisBytes must not be negative")
+        return max(0, int(override) - int(held))
+    return max(0, int(BASIS_SAFETY * (int(hbm_free) + int(reusable))))
+
+
+def split_combinations(nc):
+    """``[(first, width), ...]``: the calls that serve a table of ``nc`` combinations per column from a kept basis, widest
+    first (11 -> 8 + 2 + 1)."""
+    nc = int(nc)
+    if nc < 1:
+        raise ValueError("at least one combination per column")
+    out, lo = [], 0
+    while lo < nc:
+        w = next(w for w in BASIS_COMBINE_WIDTHS if w <= nc - lo)
+        out.append((lo, w))
+        lo += w
+    return out
+
+
+def _checked_basis_mode(value, what):
+    if value not in BASIS_MODES:
+        raise ValueError(f"{what} must be one of {BASIS_MODES}, not {value!r}")
+    return value
+
+
+def _checked_tables(G, ncols, steps, kept):
+    """The coefficient tables as contiguous ``[m_r, NC]`` arrays and NC; ``steps[r]``: the steps column r ran; ``kept``:
+    every group has its basis (any NC), else the product pass has to serve some (NC = 1 or 2)."""
+    if len(G) != ncols:
+        raise ValueError("one coefficient table per column")
+    tabs = [np.asarray(g, dtype=np.float64) for g in G]
+    tabs = [np.ascontiguousarray(t[:, None] if t.ndim == 1 else t) for t in tabs]
+    nc = {t.shape[1] for t in tabs}
+    if len(nc) != 1 or next(iter(nc)) < 1:
+        raise ValueError("coefficient tables of one width, NC >= 1")
+    nc = next(iter(nc))
+    if nc not in (1, 2) and not kept:
+        raise ValueError("coefficient tables of one width, NC = 1 or 2 (wider tables need a kept basis in every group)")
+    for r, t in enumerate(tabs):
+        if len(t) > steps[r]:
+            raise ValueError(f"column {r}: {len(t)} coefficients but the run took {steps[r]} steps")
+    return tabs, nc
+
+
+def _release_bases(ctx, bases):
+    from . import _lib
+    for g, h in enumerate(bases):
+        if h is not None:
+            bases[g] = None
+            _lib.call("hipeig_lanczos_basis_release", ctx.handle, h)
 
 LanczosScalars = collections.namedtuple("LanczosScalars", "alphas betas iterations estimates converged")
 
@@ -209,39 +275,72 @@ def lanczos_filter_host(matvec, B, shifts, weights, rtol, atol, maxiter, sign=1.
 class LanczosRun:
     """Pass 1's result for the columns ``B``: ``scalars[r]`` (a ``LanczosScalars``), ``info[r]`` (0, or the step limit when
     a shift of column r was still live there), ``groups`` (the column ranges of the calls of <= 8) and
-    ``products_pass1[g]`` (block products of group g).  ``combine(G)`` is pass 2."""
+    ``products_pass1[g]`` (block products of group g).  ``combine(G)`` is pass 2.  After ``lanczos_run(keepBasis=True)``
+    ``basis_kept[g]`` tells whether group g's Lanczos vectors stayed in device memory, ``basis_bytes`` what they hold and
+    ``release()`` gives them back; ``combine`` then streams over them instead of repeating the products."""
 
     def __init__(self, H, B, shifts, sign):
         self.H, self.B, self.shifts, self.sign = H, list(B), list(shifts), sign
         self.scalars, self.info, self.groups, self.products_pass1, self.products_pass2 = [], [], [], [], []
+        self._bases = []                                  # per group: the basis handle, or None
+        self._finalizer = weakref.finalize(self, _release_bases, self.B[0].ctx, self._bases)
 
     @property
     def converged(self):
         return all(i == 0 for i in self.info)
 
+    @property
+    def basis_kept(self):
+        return [h is not None for h in self._bases]
+
+    def _basis_info(self, g):
+        from . import _lib
+        info = (C.c_int64 * 8)()
+        _lib.call("hipeig_lanczos_basis_info", self.B[0].ctx.handle, self._bases[g], info)
+        return list(info)
+
+    @property
+    def basis_bytes(self):
+        """Bytes of device memory the kept bases hold."""
+        return sum(self._basis_info(g)[1] for g, h in enumerate(self._bases) if h is not None)
+
+    def release(self):
+        """Give the kept bases back to the context (which reuses their segments); ``combine`` then takes the product pass."""
+        _release_bases(self.B[0].ctx, self._bases)
+
     def combine(self, G):
         """``sum_i G[r][i, c] v_i`` for every column: ``G[r]`` of shape ``[m_r, NC]`` with ``m_r`` at most the steps
         column r ran.  NC = 1: a list of ``HipVector``; NC = 2: of ``HipComplexVector`` (c = 0 the real half, c = 1 the
-        imaginary one).  ``products_pass2[g]`` then holds the block products of group g: its largest ``m_r`` minus one."""
+        imaginary one); wider: a list of NC ``HipVector`` per column.  ``products_pass2[g]`` then holds the block products
+        of group g: its largest ``m_r`` minus one - or 0 where the group's basis was kept: those groups are served by one
+        stream over the stored vectors, any number of times, with NC up to 8 per call (wider tables are split).  A group
+        without a basis takes the product pass, which serves NC = 1 or 2 (``ValueError`` otherwise)."""
         from . import _lib
         from .hip_vector import HipComplexVector, _ptr_table
-        if len(G) != len(self.B):
-            raise ValueError("one coefficient table per column")
-        tabs = [np.asarray(g, dtype=np.float64) for g in G]
-        tabs = [np.ascontiguousarray(t[:, None] if t.ndim == 1 else t) for t in tabs]
-        nc = {t.shape[1] for t in tabs}
-        if len(nc) != 1 or next(iter(nc)) not in (1, 2):
-            raise ValueError("coefficient tables of one width, NC = 1 or 2")
-        nc = next(iter(nc))
+        kept = bool(self._bases) and all(h is not None for h in self._bases)
+        tabs, nc = _checked_tables(G, len(self.B), [len(s.alphas) for s in self.scalars], kept)
         ctx, n = self.B[0].ctx, len(self.B[0])
         out, self.products_pass2 = [], []
         dp = C.POINTER(C.c_double)
-        for lo, hi in self.groups:
+        for g, (lo, hi) in enumerate(self.groups):
             k = hi - lo
-            for r in range(lo, hi):
-                if len(tabs[r]) > len(self.scalars[r].alphas):
-                    raise ValueError(f"column {r}: {len(tabs[r])} coefficients but the run took {len(self.scalars[r].alphas)} steps")
             m = (C.c_int * k)(*[len(tabs[r]) for r in range(lo, hi)])
+            if g < len(self._bases) and self._bases[g] is not None:
+                be = [np.ascontiguousarray(self.scalars[r].betas, dtype=np.float64) for r in range(lo, hi)]
+                pb = (dp * k)(*[b.ctypes.data_as(dp) for b in be])
+                cols = [[None] * nc for _ in range(k)]
+                for c0, w in split_combinations(nc):
+                    part = [np.ascontiguousarray(tabs[r][:, c0:c0 + w]) for r in range(lo, hi)]
+                    pg = (dp * k)(*[t.ctypes.data_as(dp) for t in part])
+                    bufs = [ctx.alloc(n) for _ in range(k * w)]
+                    qt, keep2 = _ptr_table(bufs)
+                    _lib.call("hipeig_lanczos_basis_combine", ctx.handle, self._bases[g], k, m, pb, w, pg, qt)
+                    for j in range(k):
+                        cols[j][c0:c0 + w] = [self.B[lo + j]._new(bufs[j * w + c]) for c in range(w)]
+                self.products_pass2.append(0)
+                for j in range(k):
+                    out.append(cols[j][0] if nc == 1 else HipComplexVector(*cols[j]) if nc == 2 else cols[j])
+                continue
             al = [np.ascontiguousarray(self.scalars[r].alphas, dtype=np.float64) for r in range(lo, hi)]
             be = [np.ascontiguousarray(self.scalars[r].betas, dtype=np.float64) for r in range(lo, hi)]
             pa = (dp * k)(*[a.ctypes.data_as(dp) for a in al])
@@ -278,14 +377,30 @@ def _checked_inputs(H, B, what):
     return B
 
 
-def lanczos_run(H, B, shifts, reverseGF=False):
+def _default_basis_budget(ctx, basisBytes, held):
+    """``basis_budget`` on the context's figures: free device memory and the bytes of released bases it would reuse."""
+    from . import _lib
+    if basisBytes is not None:
+        return basis_budget(0, 0, basisBytes, held)
+    info = (C.c_int64 * 8)()
+    _lib.call("hipeig_lanczos_basis_info", ctx.handle, None, info)
+    return basis_budget(ctx.device_info()["hbm_free"], info[5])
+
+
+def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None):
     """Pass 1 on the device (``hipeig_lanczos_block_scalars``) for the real ``HipVector``s ``B`` and up to 32 ``shifts``
     (real or complex) of ``sign*(z I - H)``, ``sign = -1`` with ``reverseGF``: a ``LanczosRun``.  More than 8 columns are
     grouped into calls of 8, each in lock step on block products.  Tolerances and the step limit come from
-    ``B[0].options["linearSystemArgs"]`` as in ``solve_shifts``.  Nothing is raised here: ``run.info`` tells."""
+    ``B[0].options["linearSystemArgs"]`` as in ``solve_shifts``.  Nothing is raised here: ``run.info`` tells.
+
+    ``keepBasis``: every group keeps its Lanczos vectors in device memory (``hipeig_lanczos_block_scalars_keep``, the same
+    scalars) as long as the byte budget allows - ``basisBytes`` for the whole run, by default ``basis_budget`` of the free
+    device memory.  A group whose basis does not fit finishes as a plain pass 1; ``run.basis_kept`` tells."""
     from . import _lib
     from .hip_vector import _ptr_table
     B = _checked_inputs(H, B, "lanczos_run")
+    if basisBytes is not None and int(basisBytes) < 0:
+        raise ValueError("basisBytes must not be negative")
     zs = [complex(z) for z in np.asarray(shifts).reshape(-1)]
     if not 1 <= len(zs) <= MAX_SHIFTS_PER_RUN:
         raise ValueError(f"lanczos_run takes 1 to {MAX_SHIFTS_PER_RUN} shifts")
@@ -309,8 +424,16 @@ def lanczos_run(H, B, shifts, reverseGF=False):
         info = (C.c_int * k)()
         stats = (C.c_double * (1 + k))()
         dp = C.POINTER(C.c_double)
-        _lib.call("hipeig_lanczos_block_scalars", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
-                  alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats)
+        if keepBasis:
+            basis = C.c_void_p()
+            budget = _default_basis_budget(ctx, basisBytes, run.basis_bytes)
+            _lib.call("hipeig_lanczos_block_scalars_keep", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
+                      alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats, budget, C.byref(basis))
+            run._bases.append(C.c_void_p(basis.value) if basis.value else None)
+        else:
+            _lib.call("hipeig_lanczos_block_scalars", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
+                      alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats)
+            run._bases.append(None)
         run.groups.append((lo, hi))
         run.products_pass1.append(int(stats[0]))
         for j in range(k):
@@ -322,27 +445,48 @@ def lanczos_run(H, B, shifts, reverseGF=False):
     return run
 
 
-def lanczos_filter(H, B, shifts, weights, reverseGF=False):
+def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", basisBytes=None):
     """``[q_r]`` (``HipVector``) with ``q_r = sum_j Re(weights[j] x_{j,r})``, ``x_{j,r}`` the MINRES iterate of
     ``sign*(z_j I - H) x = B[r]`` at its own stop step - FEAST's filtered vectors with ``weights[j] = -0.5 w_j r phase_j`` -
     from two Lanczos passes on the device, no solution ever formed.  Every ``b.last_solve_stats`` = ``{"iterations":
     [per shift], "estimates": [|tau_j|], "products": block products of both passes of b's group, "products_pass1",
-    "products_pass2"}``.  A shift still live at the step limit raises ``UserWarning`` as every other solver does."""
+    "products_pass2", "basis": "kept" | "recomputed"}``.  A shift still live at the step limit raises ``UserWarning`` as
+    every other solver does.
+
+    ``basis="keep"``: group by group - pass 1 with its vectors kept, coefficients, one stream over the vectors, release - so
+    at most one group's basis is alive at a time and every group has the whole budget (``basisBytes``, default
+    ``basis_budget``).  A group whose basis does not fit is served by the product pass and reports ``"recomputed"``."""
     B = _checked_inputs(H, B, "lanczos_filter")
+    _checked_basis_mode(basis, "basis")
     if len(np.asarray(weights).reshape(-1)) != len(np.asarray(shifts).reshape(-1)):
         raise ValueError("one weight per shift")
-    run = lanczos_run(H, B, shifts, reverseGF=reverseGF)
-    G = filter_coefficients(run.scalars, run.shifts, weights, run.sign)
-    q = run.combine(G) if run.converged else None
-    for g, (lo, hi) in enumerate(run.groups):
-        p1 = run.products_pass1[g]
-        p2 = run.products_pass2[g] if q is not None else 0
-        for r in range(lo, hi):
-            B[r].last_solve_stats = {"iterations": [int(i) for i in run.scalars[r].iterations],
-                                     "estimates": [float(e) for e in run.scalars[r].estimates],
-                                     "products": p1 + p2, "products_pass1": p1, "products_pass2": p2, "group": g}
-            if q is not None:
-                q[r].last_solve_stats = B[r].last_solve_stats
-    if q is None:
+    if basis == "keep":
+        spans = [(lo, min(lo + MAX_COLUMNS_PER_CALL, len(B))) for lo in range(0, len(B), MAX_COLUMNS_PER_CALL)]
+    else:
+        spans = [(0, len(B))]                                       # every group's pass 1 first, then every pass 2
+    q, converged = [], True
+    for first, (lo, hi) in enumerate(spans):
+        run = lanczos_run(H, B[lo:hi], shifts, reverseGF=reverseGF, keepBasis=basis == "keep", basisBytes=basisBytes)
+        try:
+            G = filter_coefficients(run.scalars, run.shifts, weights, run.sign)
+            part = run.combine(G) if run.converged else None
+            kept = run.basis_kept
+        finally:
+            run.release()
+        converged = converged and part is not None
+        for g, (glo, ghi) in enumerate(run.groups):
+            p1 = run.products_pass1[g]
+            p2 = run.products_pass2[g] if part is not None else 0
+            for r in range(glo, ghi):
+                b = B[lo + r]
+                b.last_solve_stats = {"iterations": [int(i) for i in run.scalars[r].iterations],
+                                      "estimates": [float(e) for e in run.scalars[r].estimates],
+                                      "products": p1 + p2, "products_pass1": p1, "products_pass2": p2, "group": first + g,
+                                      "basis": "kept" if kept[g] else "recomputed"}
+                if part is not None:
+                    part[r].last_solve_stats = b.last_solve_stats
+        if part is not None:
+            q.extend(part)
+    if not converged:
         raise UserWarning("Warning:: Iterative solver is not converged ")
     return q

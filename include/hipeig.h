@@ -348,6 +348,32 @@ int hipeig_lanczos_block_combine(hipeig_ctx* ctx, hipeig_csr* A, int k, const do
                                  const double* const* alphas, const double* const* betas, int nc,
                                  const double* const* G, double* const* q, double* out_stats);
 
+/* The same pass 1 with its Lanczos vectors KEPT in device memory (lanczos_filter.py, lanczos_run(keepBasis=True)): step k's
+ * new vector goes to slot k + 1 of a basis carved from segments allocated while the run advances (HIPEIG_LF_SEGMENT slots
+ * each, default 32) instead of over the oldest of three ring buffers - the same kernels on the same operands, so every
+ * result equals hipeig_lanczos_block_scalars' (bit for bit with the row-owner sweep).  basis_bytes: byte budget of the
+ * segments.  When the next segment would exceed it, or the device has no room, the run goes on in the ring and *basis is
+ * NULL (not an error); otherwise *basis owns the vectors until hipeig_lanczos_basis_release.                          */
+typedef struct hipeig_lanczos_basis hipeig_lanczos_basis;
+int hipeig_lanczos_block_scalars_keep(hipeig_ctx* ctx, hipeig_csr* A, double sign, int k, const double* const* b,
+                                      int nshift, const double* zr, const double* zi, double rtol, double atol,
+                                      int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
+                                      int* info, double* out_stats, int64_t basis_bytes, hipeig_lanczos_basis** basis);
+/* PASS 2 from a kept basis (lanczos_filter.py, LanczosRun.combine): q[j*nc + c] = sum_{i < m[j]} G[j][i*nc + c] v_i for
+ * c < nc (1, 2, 4 or 8), v_i = r_i / betas[j][i], in one stream over the stored vectors - no operator product, any number
+ * of calls per basis.  k must be the basis's column count, m[j] at most the vectors kept for column j; betas[j]: host
+ * array of at least m[j] doubles (pass 1's).  With the row-owner sweep the result equals hipeig_lanczos_block_combine's
+ * bit for bit.                                                                                                        */
+int hipeig_lanczos_basis_combine(hipeig_ctx* ctx, const hipeig_lanczos_basis* basis, int k, const int* m,
+                                 const double* const* betas, int nc, const double* const* G, double* const* q);
+/* What a kept basis holds (lanczos_filter.py, LanczosRun.basis_bytes and default_basis_budget): info[0] vectors kept (the
+ * largest column's), [1] bytes of its segments, [2] interleave width K, [3] rows, [4] columns, [5] bytes of released
+ * segments the context would hand out again, [6] segments, [7] slots per segment.  basis may be NULL: only [5] is set. */
+int hipeig_lanczos_basis_info(hipeig_ctx* ctx, const hipeig_lanczos_basis* basis, int64_t info[8]);
+/* Give a kept basis's segments back to the context for reuse (lanczos_filter.py, LanczosRun.release); basis may be NULL.
+ * The context frees them when an allocation fails and when it is destroyed.                                           */
+int hipeig_lanczos_basis_release(hipeig_ctx* ctx, hipeig_lanczos_basis* basis);
+
 /* ---- timing on the library's compute stream (HIP events) --------------------------- */
 int hipeig_timer_start(hipeig_ctx* ctx);
 int hipeig_timer_stop(hipeig_ctx* ctx, float* elapsed_ms);   /* synchronous */

@@ -4,16 +4,21 @@ subspace vectors, 16 Legendre nodes = 8 contour points, window [-0.21, 0.21], in
 ``gcrotmk`` path as it stands (one contour point at a time, its 16 solves in lock step) and with
 ``linearSolver="minres_shifted"`` (one shared-Lanczos solve per subspace vector for all 8 points) and with
 ``linearSolver="lanczos_filter"`` (mode ``filter``: the filtered vectors from two Lanczos passes, 8 vectors in lock step
-on block products, no per-shift vector), the modes alternating.  One JSON line per run as soon as it is measured; the first line describes the device.
+on block products, no per-shift vector) and with the same plus ``"lanczosBasis": "keep"`` (mode ``basis``: pass 1 keeps its
+vectors in device memory and pass 2 is one stream over them), the modes alternating.  One JSON line per run as soon as it
+is measured; the first line describes the device.
 
 Then the per-phase split of one shared solve (``--phases``, default on): the whole 8-shift solve of the first subspace
 vector timed with ``hipeig_timer_*``, and each of its three kernels alone (HIPEIG_MS_PROBE = 1 sweep / 2 second kernel /
 3 update pass: that kernel launched ``--probe-steps`` times on a state record that does not advance), next to
 ``hipeig_spmv`` at the same size and to the update pass's byte model (8 n + 80 n per live shift).  For the ``filter`` mode:
 one 8-column run with pass 1, the host's coefficients and pass 2 timed apart, pass 1's three kernels alone
-(HIPEIG_LF_PROBE = 1 sweep / 2 second kernel / 3 scalar kernel), and the block sweep's time per column.
+(HIPEIG_LF_PROBE = 1 sweep / 2 second kernel / 3 scalar kernel), and the block sweep's time per column.  For the ``basis``
+mode: one 8-column run with the keeping pass 1 and the combination from the kept basis timed apart - the combination's ms
+per group and its TB/s against the byte model 8 n K m + 8 n K NC (m slots read, NC outputs written), for NC = 1, 2 and 8 -
+and the bytes the basis holds.
 
-    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted,filter] >> profiles/NN_shifted_feast.jsonl
+    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted,filter,basis] >> profiles/NN_shifted_feast.jsonl
 
 ``--cpu``: instead, the NumPy twins on the host generator's operator (small N): products per shift of the shared-Lanczos
 solver, and the two-pass filter's products and its difference from the former's sum; no timing claims;
@@ -45,6 +50,7 @@ def main():
     ap.add_argument("--cols", type=int, default=4, help="arnoldiColumnsPerPass of the gcrotmk mode")
     ap.add_argument("--phases", type=int, default=1)
     ap.add_argument("--probe-steps", type=int, default=200)
+    ap.add_argument("--basis-bytes", type=int, default=None, help="byte budget of the basis mode (default: the library's rule)")
     ap.add_argument("--label", default="")
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--cpu-gcrotmk", action="store_true", help="with --cpu: also count SciPy gcrotmk's products per point")
@@ -99,7 +105,11 @@ def main():
     lsa = {"gcrotmk": {"linearSolver": "gcrotmk", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7,
                        "arnoldiColumnsPerPass": a.cols},
            "shifted": {"linearSolver": "minres_shifted", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7},
-           "filter": {"linearSolver": "lanczos_filter", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7}}
+           "filter": {"linearSolver": "lanczos_filter", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7},
+           "basis": {"linearSolver": "lanczos_filter", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7}}
+    extra = {"basis": {"lanczosBasis": "keep"}}
+    if a.basis_bytes is not None:
+        extra["basis"]["lanczosBasisBytes"] = a.basis_bytes
     Y0 = la.qr(rng.standard_normal((N, m0)), mode="economic")[0]
     ctx = ea.HipContext.default()
     print(json.dumps({"device": ctx.device_info()["name"], "N": N, "m0": m0, "contour_points": a.nc // 2, "reps": a.reps,
@@ -122,7 +132,8 @@ def main():
     for rep in range(a.reps):
         for mode in (modes if rep % 2 == 0 else modes[::-1]):
             counts.update(pairs=0, single=0)
-            Y = [ea.HipVector(Y0[:, i].copy(), {"linearSystemArgs": dict(lsa[mode])}, ctx=ctx) for i in range(m0)]
+            Y = [ea.HipVector(Y0[:, i].copy(), dict(extra.get(mode, {}), linearSystemArgs=dict(lsa[mode])), ctx=ctx)
+                 for i in range(m0)]
             ctx.synchronize()
             t0 = time.perf_counter()
             with warnings.catch_warnings():
@@ -139,10 +150,10 @@ def main():
                             "iterations_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk)),
                                                               int(max(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk))]
                                                              for kk in range(a.nc // 2)]})
-            elif mode == "filter":
+            elif mode in ("filter", "basis"):
                 rec = st["lanczosFilter"][0]
                 row.update({"runs": rec["runs"], "block_products_pass1": rec["products_pass1"],
-                            "block_products_pass2": rec["products_pass2"],
+                            "block_products_pass2": rec["products_pass2"], "basis": rec["basis"],
                             "steps_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["steps"]) if k == kk)),
                                                          int(max(i for (k, v), i in zip(rec["pairs"], rec["steps"]) if k == kk))]
                                                         for kk in range(a.nc // 2)]})
@@ -246,6 +257,53 @@ def main():
                           "second_kernel_ms": round(phase["second_kernel"], 5), "scalar_kernel_ms": round(phase["scalar_kernel"], 5),
                           "sweep_ms_per_column": round(phase["sweep"] / K, 5), "hipeig_spmv_ms": round(spmv_ms, 5),
                           "second_kernel_TBps": round(24 * N * K / (phase["second_kernel"] * 1e-3) / 1e12, 3)}), flush=True)
+
+    if a.phases and "basis" in modes:
+        import importlib
+        import math
+        from eigensolvers_amd import feast as pf
+        lf = importlib.import_module("eigensolvers_amd.lanczos_filter")
+        zs = contour(a.nc)
+        gk, wk = pf.quadraturePointsWeights(a.nc, "legendre", positiveHalf=True)
+        ws = [-0.5 * w * 0.21 * (math.cos(pf.contour_point(-0.21, 0.21, g)[0]) + 1j * math.sin(pf.contour_point(-0.21, 0.21, g)[0]))
+              for g, w in zip(gk, wk)]
+        K = min(8, m0)
+        B = [ea.HipVector(Y0[:, i].copy(), {"linearSystemArgs": dict(lsa["basis"])}, ctx=ctx) for i in range(K)]
+        os.environ.pop("HIPEIG_LF_PROBE", None)
+        ea.lanczos_filter(H, B, zs, ws, basis="keep", basisBytes=a.basis_bytes)   # warm (workspace, operator copy, reusable segments)
+        ctx.timer_start()
+        run = ea.lanczos_run(H, B, zs, keepBasis=True, basisBytes=a.basis_bytes)
+        pass1_ms = ctx.timer_stop()
+        kept, held = run.basis_kept, run.basis_bytes
+        t0 = time.perf_counter()
+        G = lf.filter_coefficients(run.scalars, zs, ws)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        width = 4 if K <= 4 else 8
+        m = max(len(g) for g in G)
+        row = {"label": a.label, "N": N, "mode": "basis_phases", "columns": K, "shifts": len(zs),
+               "block_variant": H.block_info()["variant"], "basis_kept": kept, "basis_bytes": held,
+               "block_products_pass1": run.products_pass1[0], "pass1_keep_ms": round(pass1_ms, 3),
+               "pass1_keep_ms_per_step": round(pass1_ms / run.products_pass1[0], 5),
+               "host_coefficients_ms": round(host_ms, 3), "slots_read": m}
+        rng2 = np.random.default_rng(3)
+        for nc in (1, 2, 8):
+            if nc > 2 and not all(kept):
+                continue                                            # the product pass serves NC = 1 and 2 only
+            Gn = G if nc == 1 else [np.repeat(g, nc, axis=1) * rng2.standard_normal((1, nc)) for g in G]
+            times = []
+            for _ in range(max(3, a.reps)):
+                ctx.timer_start()
+                run.combine(Gn)
+                times.append(ctx.timer_stop())
+            model = 8.0 * N * width * m + 8.0 * N * width * nc
+            best, med = min(times), sorted(times)[len(times) // 2]
+            row.update({f"combine_nc{nc}_ms_per_group": [round(t, 3) for t in times],
+                        f"combine_nc{nc}_ms_median": round(med, 3), f"combine_nc{nc}_model_bytes": int(model),
+                        f"combine_nc{nc}_TBps_median": round(model / (med * 1e-3) / 1e12, 3),
+                        f"combine_nc{nc}_TBps_best": round(model / (best * 1e-3) / 1e12, 3)})
+            row[f"block_products_pass2_nc{nc}"] = run.products_pass2[0]
+        run.release()
+        print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":
