@@ -112,6 +112,10 @@ SIGNATURES = {
     "hipeig_lanczos_block_scalars_keep": [_P, _P, _D, C.c_int, _PP, C.c_int, _DP, _DP, _D, _D, C.c_int, _DP, _DP, _IP, _DP,
                                           _IP, _DP, _I64, _PP],
     "hipeig_lanczos_basis_combine": [_P, _P, C.c_int, _IP, C.POINTER(_DP), C.c_int, C.POINTER(_DP), _PP],
+    "hipeig_lanczos_block_scalars_prefix": [_P, _P, _D, C.c_int, _PP, C.c_int, _DP, _DP, _D, _D, C.c_int, _DP, _DP, _IP, _DP,
+                                            _IP, _DP, _I64, _PP],
+    "hipeig_lanczos_basis_combine_tail": [_P, _P, _P, C.c_int, _IP, C.POINTER(_DP), C.POINTER(_DP), C.c_int,
+                                          C.POINTER(_DP), _PP, _DP],
     "hipeig_lanczos_basis_info": [_P, _P, _I64P],
     "hipeig_lanczos_basis_release": [_P, _P],
     "hipeig_csr_set_block_variant": [_P, C.c_int],

@@ -19,6 +19,9 @@
 //
 // Keep mode (hipeig_lanczos_block_scalars_keep): pass 1 leaves every r_k in a slot of a basis in device memory instead of
 // a ring of three, and pass 2 (hipeig_lanczos_basis_combine) is one stream over the slots - see "kept basis" below.
+// Prefix mode (hipeig_lanczos_block_scalars_prefix): a basis that outgrows its byte budget keeps the first p vectors, and
+// pass 2 (hipeig_lanczos_basis_combine_tail) is the stream for the terms i < p - 1 plus the recurrence from step p - 1.
+#include <limits.h>
 #include <math.h>
 #include "spmm_device.h"
 
@@ -225,14 +228,21 @@ lf_scalar_kernel(LfState* __restrict__ S, LfShifts a, const double* __restrict__
 // alpha_i / beta_i [K], G[i][K][NC] - formed on the host with the divisions pass 1's kernels make.
 #define LF_TAB(K, NC) ((K) * (3 + (NC)))
 
+// Doubles of workspace the tail pass of a prefix basis takes at most (lf_combine_tail_impl): the state record's area, the
+// stream's and the product steps' tables for `steps` steps in all, two work vectors and NC packed combinations.
+static int64_t lf_tail_doubles(int K, int NC, int64_t steps, int64_t nb) {
+  const int64_t tab_d = (steps * (LF_TAB(K, NC) + K * (1 + NC) + 1) + 3 * K + 31) & ~(int64_t)31;
+  return LF_HEAD_DOUBLES + tab_d + (2 + NC) * nb;
+}
+
 template <int K, int NC>
 struct LfCombineEpilogue {
-  double s, c1, c, g0, g1;
+  double s, c1, c, g[NC];                                    // g[cc]: this thread's column, combination cc
   int acc_on, upd_on;                                        // i < m_r ; i + 1 < m_r
   const double* __restrict__ rk;
   double* __restrict__ rkm1;                                 // r_{i-1}, overwritten by r_{i+1} (same element, same thread)
-  double* __restrict__ q0;
-  double* __restrict__ q1;
+  double* __restrict__ Q;                                    // NC packed blocks, nb doubles apart
+  int64_t nb;
   // explicit fused operations with contraction off, as MsUpd::apply: every element rounds alike wherever it is computed
   __device__ __forceinline__ void elem(int64_t r, int j, double sum, double& acc) const {
 #pragma clang fp contract(off)
@@ -240,19 +250,20 @@ struct LfCombineEpilogue {
     const double rv = rk[i];
     if (acc_on) {
       const double v = mul_rn(s, rv);
-      q0[i] = fma(g0, v, q0[i]);
-      if (NC == 2) q1[i] = fma(g1, v, q1[i]);
+#pragma unroll
+      for (int cc = 0; cc < NC; ++cc) Q[i + cc * nb] = fma(g[cc], v, Q[i + cc * nb]);
     }
     if (upd_on) rkm1[i] = fma(-c, rv, fma(-c1, rkm1[i], mul_rn(s, sum)));
   }
 };
 
+// NC <= 2 serves the product pass (hipeig_lanczos_block_combine); the tail of a prefix basis takes NC up to 8 - the
+// epilogue then holds NC coefficients per thread and makes NC read-modify-writes of Q per element, nothing else changes.
 template <int VARIANT, int K, int NC>
 __global__ void __launch_bounds__(VARIANT == 2 ? BCOO_THREADS : HIPEIG_BLOCK)
 lf_combine_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                   const double* __restrict__ val, int64_t nrows, const double* __restrict__ tab, const int* __restrict__ m,
-                  int step, const double* __restrict__ rk, double* __restrict__ rkm1, double* __restrict__ q0,
-                  double* __restrict__ q1) {
+                  int step, const double* __restrict__ rk, double* __restrict__ rkm1, double* __restrict__ Q, int64_t nb) {
   __shared__ double sh_tab[LF_TAB(K, NC)];
   __shared__ int sh_m[K];
   extern __shared__ double bcoo_lds[];
@@ -262,9 +273,10 @@ lf_combine_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t*
   LfCombineEpilogue<K, NC> epi;
   const int j = threadIdx.x % K;
   epi.s = sh_tab[j]; epi.c1 = sh_tab[K + j]; epi.c = sh_tab[2 * K + j];
-  epi.g0 = sh_tab[3 * K + j * NC]; epi.g1 = (NC == 2) ? sh_tab[3 * K + j * NC + 1] : 0.0;
+#pragma unroll
+  for (int cc = 0; cc < NC; ++cc) epi.g[cc] = sh_tab[3 * K + j * NC + cc];
   epi.acc_on = step < sh_m[j]; epi.upd_on = step + 1 < sh_m[j];
-  epi.rk = rk; epi.rkm1 = rkm1; epi.q0 = q0; epi.q1 = q1;
+  epi.rk = rk; epi.rkm1 = rkm1; epi.Q = Q; epi.nb = nb;
   double acc = 0.0;
   if (VARIANT == 2) bcoo_wg_sweep<K>(T, rk, epi, acc, bcoo_lds);
   else csr_rowowner_block_sweep<K>(rowptr, col, val, nrows, rk, epi, acc);
@@ -274,15 +286,15 @@ lf_combine_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t*
 template <int K, int NC>
 __global__ void __launch_bounds__(HIPEIG_BLOCK)
 lf_last_term_kernel(int64_t n, const double* __restrict__ tab, const int* __restrict__ m, int step,
-                    const double* __restrict__ rk, double* __restrict__ q0, double* __restrict__ q1) {
+                    const double* __restrict__ rk, double* __restrict__ Q, int64_t nb) {
 #pragma clang fp contract(off)
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n * K; i += stride) {
     const int j = (int)(i % K);
     if (step >= m[j]) continue;
     const double v = mul_rn(tab[j], rk[i]);
-    q0[i] = fma(tab[3 * K + j * NC], v, q0[i]);
-    if (NC == 2) q1[i] = fma(tab[3 * K + j * NC + 1], v, q1[i]);
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) Q[i + cc * nb] = fma(tab[3 * K + j * NC + cc], v, Q[i + cc * nb]);
   }
 }
 
@@ -319,6 +331,7 @@ struct hipeig_lanczos_basis {
   int64_t n, nb, nrows;                                       // nb: doubles per slot; nrows: the operator's
   size_t seg_bytes;
   int steps[BCOO_KMAX];                                       // vectors kept per column: v_0 .. v_{steps - 1}
+  int ran[BCOO_KMAX];                                         // steps the column ran: more than `steps` behind a prefix
   double** seg;
 };
 
@@ -393,16 +406,23 @@ static void lf_basis_free(hipeig_ctx* c, hipeig_lanczos_basis* B) {
 
 // keep != nullptr: keep mode with `budget` bytes for the segments; *keep receives the basis, or nullptr when it was not kept
 // (budget or device memory ran out: the run went on in the ring of three, same kernels, same operands, same scalars).
+// prefix: when the next segment is refused the ones held stay and are written to their last slot, p = nseg * seg_slots
+// vectors; vector i >= p lives in ring buffer i % 3, so the hand-over is a choice of pointers at enqueue time - steps
+// p - 1 and p read their operands from the slots - and may fall inside a chunk.
 template <int K>
 static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b, int nshift,
                            const double* zr, const double* zi, double rtol, double atol, int maxiter, double* alphas,
                            double* betas, int* iterations, double* estimates, int* info, double* out_stats,
-                           int64_t budget, hipeig_lanczos_basis** keep) {
+                           int64_t budget, hipeig_lanczos_basis** keep, int prefix) {
   const int64_t n = A->nrows;
   const int64_t nb = ((n * K + 31) & ~(int64_t)31);
   const int64_t ld = maxiter;
   const int64_t tabs = ((int64_t)K * (2 * ld + 1) + 31) & ~(int64_t)31;
-  if (lf_reserve(c, LF_HEAD_DOUBLES + tabs + 3 * nb)) return 1;
+  int64_t need = LF_HEAD_DOUBLES + tabs + 3 * nb;
+  // a prefix is followed by a tail pass: its workspace (NC <= 2) is taken before the first segment, so that the basis
+  // cannot eat the room of the pass it serves
+  if (keep && prefix && lf_tail_doubles(K, 2, maxiter, nb) > need) need = lf_tail_doubles(K, 2, maxiter, nb);
+  if (lf_reserve(c, need)) return 1;
   if (!c->h_lf_state) HIPEIG_CHECK(hipHostMalloc((void**)&c->h_lf_state, sizeof(LfState), hipHostMallocDefault));
   LfState* V = reinterpret_cast<LfState*>(c->lf_ws);
   double* d_alphas = c->lf_ws + LF_HEAD_DOUBLES;
@@ -495,12 +515,16 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   };
 
   int steps = 0;
+  int cap = INT_MAX;                                          // prefix mode, once a segment was refused: the slots held
+  auto vec = [&](int i) { return (kept.B && i < cap) ? lf_slot(kept.B, i) : R[i % 3]; };
   while (steps < maxiter) {
     const int kend = (steps + chunk < maxiter) ? steps + chunk : maxiter;
     // the segments this chunk writes (slots up to kend) before it is enqueued; when the budget or the device says no, the
-    // two live vectors move to the ring and the run goes on as plain pass 1
-    while (kept.B && kept.B->nseg * kept.B->seg_slots <= kend)
+    // two live vectors move to the ring and the run goes on as plain pass 1 - or, in prefix mode, the slots held are all
+    // there will be (slot `steps` exists: cap > steps)
+    while (kept.B && cap == INT_MAX && kept.B->nseg * kept.B->seg_slots <= kend)
       if (lf_basis_grow(c, kept.B, budget)) {
+        if (prefix) { cap = kept.B->nseg * kept.B->seg_slots; break; }
         HIPEIG_CHECK(hipMemcpyAsync(R[steps % 3], lf_slot(kept.B, steps), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         if (steps)
           HIPEIG_CHECK(hipMemcpyAsync(R[(steps + 2) % 3], lf_slot(kept.B, steps - 1), (size_t)nb * sizeof(double),
@@ -510,9 +534,9 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
       }
     for (; steps < kend; ++steps) {
       const int kk = probe ? 0 : steps;
-      double* rk = kept.B ? lf_slot(kept.B, kk) : R[kk % 3];
-      double* w = kept.B ? lf_slot(kept.B, kk + 1) : R[(kk + 1) % 3];
-      double* rkm1 = kept.B ? lf_slot(kept.B, kk ? kk - 1 : 0) : R[(kk + 2) % 3];   // step 0 reads no r_{-1}
+      double* rk = vec(kk);
+      double* w = vec(kk + 1);
+      double* rkm1 = kk ? vec(kk - 1) : kept.B ? lf_slot(kept.B, 0) : R[2];         // step 0 reads no r_{-1}
       if (!probe || probe == 1) enqueue_sweep(rk, rkm1, w);
       if (!probe || probe == 2)
         hipLaunchKernelGGL(lf_kc_kernel<K>, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, (const LfState*)V,
@@ -545,12 +569,13 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
     }
     info[j] = (probe || any) ? maxiter : 0;
     if (out_stats) out_stats[1 + j] = m;
-    if (kept.B) kept.B->steps[j] = m;
+    if (kept.B) { kept.B->steps[j] = m < cap ? m : cap; kept.B->ran[j] = m; }
   }
   if (out_stats) out_stats[0] = probe ? maxiter : products;
   if (hipeig_sync_checked(c)) return 4;
   if (kept.B) {                                               // memory follows the steps taken: slots 0 .. products - 1
-    lf_basis_trim(c, kept.B, (products + kept.B->seg_slots - 1) / kept.B->seg_slots);
+    const int held = products < cap ? products : cap;        // a run that stopped before the cap holds a whole basis
+    lf_basis_trim(c, kept.B, (held + kept.B->seg_slots - 1) / kept.B->seg_slots);
     *keep = kept.B;
     kept.B = nullptr;
   }
@@ -560,7 +585,7 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
 static int lf_scalars_entry(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b, int nshift,
                             const double* zr, const double* zi, double rtol, double atol, int maxiter, double* alphas,
                             double* betas, int* iterations, double* estimates, int* info, double* out_stats, int64_t budget,
-                            hipeig_lanczos_basis** keep) {
+                            hipeig_lanczos_basis** keep, int prefix) {
   HIPEIG_REQUIRE(b && zr && zi && alphas && betas && iterations && estimates && info, "null argument");
   HIPEIG_REQUIRE(k >= 1 && k <= BCOO_KMAX, "1 to 8 right-hand sides per call");
   HIPEIG_REQUIRE(nshift >= 1 && nshift <= LF_MAX_SHIFTS, "1 to 32 shifts per run");
@@ -578,9 +603,9 @@ static int lf_scalars_entry(hipeig_ctx* c, hipeig_csr* A, double sign, int k, co
   if (A->nrows == 0) return 0;
   if (lf_width(k) == 4)
     return lf_scalars_impl<4>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                              out_stats, budget, keep);
+                              out_stats, budget, keep, prefix);
   return lf_scalars_impl<8>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                            out_stats, budget, keep);
+                            out_stats, budget, keep, prefix);
 }
 
 extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
@@ -588,7 +613,7 @@ extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double
                                             int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
                                             int* info, double* out_stats) {
   return lf_scalars_entry(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                          out_stats, 0, nullptr);
+                          out_stats, 0, nullptr, 0);
 }
 
 extern "C" int hipeig_lanczos_block_scalars_keep(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
@@ -600,7 +625,82 @@ extern "C" int hipeig_lanczos_block_scalars_keep(hipeig_ctx* c, hipeig_csr* A, d
   *basis = nullptr;
   HIPEIG_REQUIRE(basis_bytes >= 0, "negative byte budget");
   return lf_scalars_entry(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                          out_stats, basis_bytes, basis);
+                          out_stats, basis_bytes, basis, 0);
+}
+
+// Keep mode that holds on to a prefix: see lf_scalars_impl.
+extern "C" int hipeig_lanczos_block_scalars_prefix(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
+                                                   int nshift, const double* zr, const double* zi, double rtol, double atol,
+                                                   int maxiter, double* alphas, double* betas, int* iterations,
+                                                   double* estimates, int* info, double* out_stats, int64_t basis_bytes,
+                                                   hipeig_lanczos_basis** basis) {
+  HIPEIG_REQUIRE(basis != nullptr, "null argument");
+  *basis = nullptr;
+  HIPEIG_REQUIRE(basis_bytes >= 0, "negative byte budget");
+  return lf_scalars_entry(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
+                          out_stats, basis_bytes, basis, 1);
+}
+
+// Table records of the product steps `first` .. m[j] - 1 of every column, record i at t0 + (i - first) * LF_TAB.
+template <int K, int NC>
+static void lf_fill_product_tab(double* t0, int first, int k, const int* m, const double* const* alphas,
+                                const double* const* betas, const double* const* G) {
+  for (int j = 0; j < k; ++j)
+    for (int i = first; i < m[j]; ++i) {
+      double* t = t0 + (int64_t)(i - first) * LF_TAB(K, NC);
+      t[j] = 1.0 / betas[j][i];                                // the divisions of pass 1: LfCol::s, the sweep's c1, KC's c
+      t[K + j] = i ? betas[j][i] / betas[j][i - 1] : 0.0;
+      t[2 * K + j] = alphas[j][i] / betas[j][i];
+      for (int cc = 0; cc < NC; ++cc) t[3 * K + j * NC + cc] = G[j][(size_t)i * NC + cc];
+    }
+}
+
+// Steps first .. mmax - 2 with a product each, then the last term: vector i lives in Vb[i & 1] (Vb[first & 1] = r_first,
+// the other r_{first-1}, zeros at first = 0); d_tab holds the records from `first` on, Q the NC packed sums so far.
+template <int K, int NC>
+static int lf_enqueue_products(hipeig_ctx* c, hipeig_csr* A, const double* d_tab, const int* d_m, int first, int mmax,
+                               double* const* Vb, double* Q, int64_t nb) {
+  const int64_t n = A->nrows;
+  const int bv = hipeig_block_pick_variant(c, A, K, 1);
+  if (bv < 0) return 1;
+  const BlockedLayout& L = A->b[layout_slot(K)];
+  const BcooView tview = hipeig_bcoo_view(A, L);
+  if (bv == 2)
+    HIPEIG_CHECK(hipFuncSetAttribute((const void*)lf_combine_kernel<2, K, NC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)HIPEIG_BCOO_LDS_MAX));
+  const SweepGrid sg = (bv == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
+  for (int i = first; i + 1 < mmax; ++i) {
+    const double* tab = d_tab + (int64_t)(i - first) * LF_TAB(K, NC);
+    const double* rk = Vb[i & 1];
+    double* rkm1 = Vb[(i + 1) & 1];
+    if (bv == 2) {
+      BcooView tv = tview;
+      for (int sw = 0; sw < sg.launches; ++sw) {
+        tv.unit_begin = sw * sg.wgs;
+        hipLaunchKernelGGL((lf_combine_kernel<2, K, NC>), dim3(sg.wgs), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream,
+                           tv, A->d_rowptr, A->d_col, A->d_val, n, tab, d_m, i, rk, rkm1, Q, nb);
+      }
+    } else {
+      hipLaunchKernelGGL((lf_combine_kernel<1, K, NC>), dim3(sg.wgs), dim3(HIPEIG_BLOCK), 0, c->stream, tview, A->d_rowptr,
+                         A->d_col, A->d_val, n, tab, d_m, i, rk, rkm1, Q, nb);
+    }
+  }
+  hipLaunchKernelGGL((lf_last_term_kernel<K, NC>), dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream, n,
+                     d_tab + (int64_t)(mmax - 1 - first) * LF_TAB(K, NC), d_m, mmax - 1, (const double*)Vb[(mmax - 1) & 1], Q,
+                     nb);
+  HIPEIG_CHECK(hipGetLastError());
+  return 0;
+}
+
+// q[j * NC + cc] <- column j of packed block cc of Q
+template <int K, int NC>
+static int lf_unpack_combinations(hipeig_ctx* c, int64_t n, int k, const double* Q, int64_t nb, double* const* q) {
+  for (int cc = 0; cc < NC; ++cc) {
+    double* part[BCOO_KMAX];
+    for (int j = 0; j < k; ++j) part[j] = q[j * NC + cc];
+    if (hipeig_block_unpack(c, K, n, k, Q + (int64_t)cc * nb, part)) return 1;
+  }
+  return 0;
 }
 
 template <int K, int NC>
@@ -621,67 +721,20 @@ static int lf_combine_impl(hipeig_ctx* c, hipeig_csr* A, int k, const double* co
   double* d_tab = c->lf_ws + LF_HEAD_DOUBLES;
   int* d_m = reinterpret_cast<int*>(d_tab + (int64_t)mmax * LF_TAB(K, NC));
   double* Vb[2] = {c->lf_ws + LF_HEAD_DOUBLES + tab_d, c->lf_ws + LF_HEAD_DOUBLES + tab_d + nb};
-  double* Q0 = c->lf_ws + LF_HEAD_DOUBLES + tab_d + 2 * nb;
-  double* Q1 = (NC == 2) ? Q0 + nb : nullptr;
+  double* Q = c->lf_ws + LF_HEAD_DOUBLES + tab_d + 2 * nb;
   double* h_tab = (double*)calloc((size_t)tab_d, sizeof(double));
   HIPEIG_REQUIRE(h_tab != nullptr, "out of host memory");
   int* h_m = reinterpret_cast<int*>(h_tab + (int64_t)mmax * LF_TAB(K, NC));
-  for (int j = 0; j < K; ++j) {
-    h_m[j] = j < k ? m[j] : 0;
-    if (j >= k || m[j] == 0) continue;
-    for (int i = 0; i < m[j]; ++i) {
-      double* t = h_tab + (int64_t)i * LF_TAB(K, NC);
-      t[j] = 1.0 / betas[j][i];                              // the divisions of pass 1: LfCol::s, the sweep's c1, KC's c
-      t[K + j] = i ? betas[j][i] / betas[j][i - 1] : 0.0;
-      t[2 * K + j] = alphas[j][i] / betas[j][i];
-      for (int cc = 0; cc < NC; ++cc) t[3 * K + j * NC + cc] = G[j][(size_t)i * NC + cc];
-    }
-  }
+  for (int j = 0; j < K; ++j) h_m[j] = j < k ? m[j] : 0;
+  lf_fill_product_tab<K, NC>(h_tab, 0, k, m, alphas, betas, G);
   hipError_t e = hipMemcpyAsync(d_tab, h_tab, (size_t)tab_d * sizeof(double), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   free(h_tab);
   HIPEIG_CHECK(e);
   if (hipeig_block_pack(c, K, n, k, b, Vb[0])) return 1;
-  const int gS = grid_stream(n * K);
   HIPEIG_CHECK(hipMemsetAsync(Vb[1], 0, (size_t)nb * (1 + NC) * sizeof(double), c->stream));
-
-  const int bv = hipeig_block_pick_variant(c, A, K, 1);
-  if (bv < 0) return 1;
-  const BlockedLayout& L = A->b[layout_slot(K)];
-  const BcooView tview = hipeig_bcoo_view(A, L);
-  if (bv == 2)
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)lf_combine_kernel<2, K, NC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)HIPEIG_BCOO_LDS_MAX));
-  const SweepGrid sg = (bv == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
-  for (int i = 0; i + 1 < mmax; ++i) {
-    const double* tab = d_tab + (int64_t)i * LF_TAB(K, NC);
-    const double* rk = Vb[i & 1];
-    double* rkm1 = Vb[(i + 1) & 1];
-    if (bv == 2) {
-      BcooView tv = tview;
-      for (int sw = 0; sw < sg.launches; ++sw) {
-        tv.unit_begin = sw * sg.wgs;
-        hipLaunchKernelGGL((lf_combine_kernel<2, K, NC>), dim3(sg.wgs), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream,
-                           tv, A->d_rowptr, A->d_col, A->d_val, n, tab, (const int*)d_m, i, rk, rkm1, Q0, Q1);
-      }
-    } else {
-      hipLaunchKernelGGL((lf_combine_kernel<1, K, NC>), dim3(sg.wgs), dim3(HIPEIG_BLOCK), 0, c->stream, tview, A->d_rowptr,
-                         A->d_col, A->d_val, n, tab, (const int*)d_m, i, rk, rkm1, Q0, Q1);
-    }
-  }
-  hipLaunchKernelGGL((lf_last_term_kernel<K, NC>), dim3(gS), dim3(HIPEIG_BLOCK), 0, c->stream, n,
-                     (const double*)(d_tab + (int64_t)(mmax - 1) * LF_TAB(K, NC)), (const int*)d_m, mmax - 1,
-                     (const double*)Vb[(mmax - 1) & 1], Q0, Q1);
-  HIPEIG_CHECK(hipGetLastError());
-  if (NC == 1) {
-    if (hipeig_block_unpack(c, K, n, k, Q0, q)) return 1;
-  } else {
-    double* half[BCOO_KMAX];
-    for (int j = 0; j < k; ++j) half[j] = q[2 * j];
-    if (hipeig_block_unpack(c, K, n, k, Q0, half)) return 1;
-    for (int j = 0; j < k; ++j) half[j] = q[2 * j + 1];
-    if (hipeig_block_unpack(c, K, n, k, Q1, half)) return 1;
-  }
+  if (lf_enqueue_products<K, NC>(c, A, d_tab, d_m, 0, mmax, Vb, Q, nb)) return 1;
+  if (lf_unpack_combinations<K, NC>(c, n, k, Q, nb, q)) return 1;
   if (hipeig_sync_checked(c)) return 4;
   if (out_stats) out_stats[0] = mmax - 1;
   return 0;
@@ -821,13 +874,107 @@ static int lf_basis_combine_impl(hipeig_ctx* c, const hipeig_lanczos_basis* B, i
   hipLaunchKernelGGL((lf_basis_combine_kernel<K, NC>), dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream, n2, mmax,
                      (const double*)d_tab, (const double* const*)d_slots, (const int*)d_m, Q, nb);
   HIPEIG_CHECK(hipGetLastError());
-  for (int cc = 0; cc < NC; ++cc) {
-    double* part[BCOO_KMAX];
-    for (int j = 0; j < k; ++j) part[j] = q[j * NC + cc];
-    if (hipeig_block_unpack(c, K, n, k, Q + (int64_t)cc * nb, part)) return 1;
-  }
+  if (lf_unpack_combinations<K, NC>(c, n, k, Q, nb, q)) return 1;
   if (hipeig_sync_checked(c)) return 4;
   return 0;
+}
+
+// ---- pass 2 from a prefix ------------------------------------------------------------------------------------------------
+// The basis holds v_0 .. v_{p-1} and the largest column wants mmax > p terms.  The terms i < p - 1 come from the stream
+// (columns masked by min(m_j, p - 1)), which leaves Q packed in the workspace; r_{p-2} and r_{p-1} are copied from their
+// slots into the two work vectors - the basis is never written, it serves any number of calls - and the product loop of
+// lf_combine_impl takes over at step p - 1: mmax - p products, then the last term.  Every element meets the mul_rn / fma
+// sequence of the product pass in ascending i (the stream's accumulator starts from 0 as the product pass's Q does), so
+// with the row-owner sweep the result is the product pass's and a whole basis's, bit for bit.
+template <int K, int NC>
+static int lf_combine_tail_impl(hipeig_ctx* c, hipeig_csr* A, const hipeig_lanczos_basis* B, int k, const int* m,
+                                const double* const* alphas, const double* const* betas, const double* const* G,
+                                double* const* q, int p, int mmax) {
+  const int64_t n = B->n, nb = B->nb;
+  constexpr int TW = LF_BC_TAB(K, NC);
+  const int ms = p - 1, first = p - 1;                        // stream terms of the longest column; first product step
+  // device tables: ms stream records, ms slot pointers, mmax - first product records, then both m[K] as ints
+  const int64_t o_slots = (int64_t)ms * TW, o_prod = o_slots + ms, o_m = o_prod + (int64_t)(mmax - first) * LF_TAB(K, NC);
+  const int64_t tab_d = (o_m + 2 * K + 31) & ~(int64_t)31;
+  HIPEIG_REQUIRE(LF_HEAD_DOUBLES + tab_d + (2 + NC) * nb <= lf_tail_doubles(K, NC, mmax, nb), "tail workspace bound");
+  if (lf_reserve(c, lf_tail_doubles(K, NC, mmax, nb))) return 1;
+  double* d_tab = c->lf_ws + LF_HEAD_DOUBLES;
+  double* Vb[2] = {d_tab + tab_d, d_tab + tab_d + nb};
+  double* Q = d_tab + tab_d + 2 * nb;
+  double* h_tab = (double*)calloc((size_t)tab_d, sizeof(double));
+  HIPEIG_REQUIRE(h_tab != nullptr, "out of host memory");
+  const double** h_slots = reinterpret_cast<const double**>(h_tab + o_slots);
+  int* h_ms = reinterpret_cast<int*>(h_tab + o_m);
+  int* h_m = h_ms + K;
+  for (int i = 0; i < ms; ++i) h_slots[i] = lf_slot(B, i);
+  for (int j = 0; j < K; ++j) {
+    h_m[j] = j < k ? m[j] : 0;
+    h_ms[j] = h_m[j] < ms ? h_m[j] : ms;
+    for (int i = 0; i < h_ms[j]; ++i) {
+      double* t = h_tab + (int64_t)i * TW;
+      t[j] = 1.0 / betas[j][i];                              // LfCol::s, as lf_combine_impl
+      for (int cc = 0; cc < NC; ++cc) t[K + j * NC + cc] = G[j][(size_t)i * NC + cc];
+    }
+  }
+  lf_fill_product_tab<K, NC>(h_tab + o_prod, first, k, m, alphas, betas, G);
+  hipError_t e = hipMemcpyAsync(d_tab, h_tab, (size_t)tab_d * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  free(h_tab);
+  HIPEIG_CHECK(e);
+  const int* d_ms = reinterpret_cast<const int*>(d_tab + o_m);
+  if (ms > 0)
+    hipLaunchKernelGGL((lf_basis_combine_kernel<K, NC>), dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream,
+                       n * (K / 2), ms, (const double*)d_tab, reinterpret_cast<const double* const*>(d_tab + o_slots), d_ms, Q,
+                       nb);
+  else
+    HIPEIG_CHECK(hipMemsetAsync(Q, 0, (size_t)nb * NC * sizeof(double), c->stream));
+  HIPEIG_CHECK(hipGetLastError());
+  HIPEIG_CHECK(hipMemcpyAsync(Vb[first & 1], lf_slot(B, first), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  if (first)
+    HIPEIG_CHECK(hipMemcpyAsync(Vb[(first + 1) & 1], lf_slot(B, first - 1), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice,
+                                c->stream));
+  else
+    HIPEIG_CHECK(hipMemsetAsync(Vb[1], 0, (size_t)nb * sizeof(double), c->stream));
+  if (lf_enqueue_products<K, NC>(c, A, d_tab + o_prod, d_ms + K, first, mmax, Vb, Q, nb)) return 1;
+  if (lf_unpack_combinations<K, NC>(c, n, k, Q, nb, q)) return 1;
+  if (hipeig_sync_checked(c)) return 4;
+  return 0;
+}
+
+extern "C" int hipeig_lanczos_basis_combine(hipeig_ctx* c, const hipeig_lanczos_basis* B, int k, const int* m,
+                                            const double* const* betas, int nc, const double* const* G, double* const* q);
+
+extern "C" int hipeig_lanczos_basis_combine_tail(hipeig_ctx* c, hipeig_csr* A, const hipeig_lanczos_basis* B, int k,
+                                                 const int* m, const double* const* alphas, const double* const* betas, int nc,
+                                                 const double* const* G, double* const* q, double* out_stats) {
+  HIPEIG_REQUIRE(A && B && m && alphas && betas && G && q, "null argument");
+  HIPEIG_REQUIRE(k == B->k, "the basis was kept for another number of columns");
+  HIPEIG_REQUIRE(nc == 1 || nc == 2 || nc == 4 || nc == 8, "1, 2, 4 or 8 combinations per column");
+  HIPEIG_REQUIRE(!c->collectives, "the Lanczos filter runs on whole vectors (no row partition)");
+  HIPEIG_REQUIRE(A->nrows == A->ncols && A->nrows == B->nrows, "the operator is not the one the basis was kept for");
+  if (out_stats) out_stats[0] = 0.0;
+  int p = 0, mmax = 0;
+  for (int j = 0; j < k; ++j) {
+    p = B->steps[j] > p ? B->steps[j] : p;
+    HIPEIG_REQUIRE(m[j] >= 0 && m[j] <= B->ran[j], "more terms than the steps the column ran");
+    mmax = m[j] > mmax ? m[j] : mmax;
+  }
+  if (mmax <= p) return hipeig_lanczos_basis_combine(c, B, k, m, betas, nc, G, q);
+  for (int j = 0; j < k; ++j) {
+    HIPEIG_REQUIRE(m[j] == 0 || (alphas[j] && betas[j] && G[j]), "null column argument");
+    for (int cc = 0; cc < nc; ++cc) HIPEIG_REQUIRE(q[j * nc + cc] != nullptr, "q must not be null");
+    for (int i = 0; i < m[j]; ++i) HIPEIG_REQUIRE(betas[j][i] > 0.0, "a Lanczos vector past a breakdown was asked for");
+  }
+#define LF_TAIL_CASE(KK, NN) \
+  if (B->K == KK && nc == NN) { \
+    const int rc = lf_combine_tail_impl<KK, NN>(c, A, B, k, m, alphas, betas, G, q, p, mmax); \
+    if (rc == 0 && out_stats) out_stats[0] = mmax - p; \
+    return rc; \
+  }
+  LF_TAIL_CASE(4, 1) LF_TAIL_CASE(4, 2) LF_TAIL_CASE(4, 4) LF_TAIL_CASE(4, 8)
+  LF_TAIL_CASE(8, 1) LF_TAIL_CASE(8, 2) LF_TAIL_CASE(8, 4) LF_TAIL_CASE(8, 8)
+#undef LF_TAIL_CASE
+  HIPEIG_REQUIRE(false, "unknown interleave width");
 }
 
 extern "C" int hipeig_lanczos_basis_combine(hipeig_ctx* c, const hipeig_lanczos_basis* B, int k, const int* m,

@@ -505,7 +505,8 @@ class HipVector(AbstractVector):
         lsa.setdefault("linear_tol", 1e-4)
         lsa.setdefault("linear_atol", 1e-4)
         self.options = {"linearSystemArgs": lsa}
-        for extra in ("orthogonalization", "blockSolve", "reduction", "contourPoolWidth", "lanczosBasis", "lanczosBasisBytes"):
+        for extra in ("orthogonalization", "blockSolve", "reduction", "contourPoolWidth", "lanczosBasis", "lanczosBasisBytes",
+                      "lanczosBasisPrefix"):
             if extra in given:
                 self.options[extra] = given[extra]
         self.last_solve_stats = None
@@ -736,12 +737,16 @@ class HipVector(AbstractVector):
         """``sum_j Re(weights[j] x_j)`` for every right-hand side of ``B`` from two Lanczos passes, no solution formed
         (``lanczos_filter.lanczos_filter``); the hook ``feastDiagonalization`` looks for when ``linearSolver`` is
         ``"lanczos_filter"``.  ``B[0].options["lanczosBasis"]`` (``"recompute"``, the default, or ``"keep"``) and
-        ``["lanczosBasisBytes"]`` choose whether pass 1 keeps its vectors for pass 2 and the byte budget of that."""
+        ``["lanczosBasisBytes"]`` choose whether pass 1 keeps its vectors for pass 2 and the byte budget of that;
+        ``["lanczosBasisPrefix"]: True`` (only with ``"keep"``, ``ValueError`` otherwise) lets a basis that outgrows the
+        budget keep the vectors that fit."""
         from .lanczos_filter import lanczos_filter
         B = list(B)
         o = B[0].options if B else {}
+        if o.get("lanczosBasisPrefix") and o.get("lanczosBasis", "recompute") != "keep":
+            raise ValueError('"lanczosBasisPrefix" keeps a prefix of a kept basis: it needs "lanczosBasis": "keep"')
         return lanczos_filter(H, B, shifts, weights, reverseGF=reverseGF, basis=o.get("lanczosBasis", "recompute"),
-                              basisBytes=o.get("lanczosBasisBytes"))
+                              basisBytes=o.get("lanczosBasisBytes"), prefix=bool(o.get("lanczosBasisPrefix", False)))
 
     BLOCK_SOLVE_MIN = 3      # fewer right-hand sides are solved one by one (measured at N = 1e6: 2 columns 0.97x, 3: 1.6x, 4: 1.95x, 8: 2.8x)
 

@@ -13,6 +13,9 @@ the coefficients of shift k's iterate in that basis - numbers that follow from t
 
 With ``keepBasis`` / ``basis="keep"`` pass 1 keeps its vectors in device memory (``hipeig_lanczos_block_scalars_keep``) and
 pass 2 is one stream over them (``hipeig_lanczos_basis_combine``): no second set of products, any number of combinations.
+With ``keepPrefix`` / ``prefix=True`` on top, a basis that outgrows its byte budget keeps its first ``p`` vectors
+(``hipeig_lanczos_block_scalars_prefix``): the stream serves the terms ``i < p - 1`` and the recurrence restarts from the
+two last kept vectors (``hipeig_lanczos_basis_combine_tail``), ``m - p`` products instead of ``m - 1``.
 
 Both passes are an operator product plus a row epilogue, so up to 8 right-hand sides advance in lock step on the
 interleaved block products of ``csrc/spmm_device.h``.  The ``*_host`` functions are the NumPy statement - the
@@ -29,7 +32,8 @@ import numpy as np
 
 __all__ = ["lanczos_scalars_host", "minres_coefficients", "filter_coefficients", "lanczos_combine_host",
            "lanczos_filter_host", "lanczos_run", "lanczos_filter", "LanczosRun", "LanczosScalars", "MAX_COLUMNS_PER_CALL",
-           "MAX_SHIFTS_PER_RUN", "basis_budget", "split_combinations", "BASIS_MODES"]
+           "MAX_SHIFTS_PER_RUN", "basis_budget", "split_combinations", "BASIS_MODES", "lanczos_vectors_host",
+           "lanczos_combine_prefix_host", "prefix_split"]
 
 MAX_COLUMNS_PER_CALL = 8
 MAX_SHIFTS_PER_RUN = 32
@@ -64,6 +68,28 @@ def split_combinations(nc):
     return out
 
 
+def prefix_split(m, p):
+    """``(stream_terms, products)`` of a combination of ``m`` terms from a basis that holds the first ``p`` vectors.
+    ``m <= p``: the stream takes all ``m`` terms, no product.  Otherwise the stream takes the terms ``i < p - 1``, the
+    recurrence restarts from ``v_{p-2}``, ``v_{p-1}`` and runs the steps ``p - 1 .. m - 2`` - ``m - p`` products - and the
+    last term needs none: ``stream_terms + products + 1 == m``."""
+    m, p = int(m), int(p)
+    if m < 0 or p < 0:
+        raise ValueError("negative number of terms or vectors")
+    if m <= p:
+        return m, 0
+    if p == 0:
+        raise ValueError("a prefix holds at least one vector")
+    return p - 1, m - p
+
+
+def _checked_prefix(prefix, keeps, what):
+    """``prefix`` only makes sense on top of a kept basis."""
+    if prefix and not keeps:
+        raise ValueError(f"{what}: keeping a prefix of the basis needs the basis to be kept")
+    return bool(prefix)
+
+
 def _checked_basis_mode(value, what):
     if value not in BASIS_MODES:
         raise ValueError(f"{what} must be one of {BASIS_MODES}, not {value!r}")
@@ -72,7 +98,8 @@ def _checked_basis_mode(value, what):
 
 def _checked_tables(G, ncols, steps, kept):
     """The coefficient tables as contiguous ``[m_r, NC]`` arrays and NC; ``steps[r]``: the steps column r ran; ``kept``:
-    every group has its basis (any NC), else the product pass has to serve some (NC = 1 or 2)."""
+    every group holds its basis or at least a prefix of it (any NC), else the product pass has to serve some (NC = 1 or
+    2)."""
     if len(G) != ncols:
         raise ValueError("one coefficient table per column")
     tabs = [np.asarray(g, dtype=np.float64) for g in G]
@@ -258,6 +285,52 @@ def lanczos_combine_host(matvec, B, alphas, betas, G):
     return out
 
 
+def lanczos_vectors_host(matvec, b, alphas, betas, p):
+    """``V[p, n]``: the first ``p`` Lanczos vectors of one column ``b`` as ``lanczos_combine_host`` rebuilds them from the
+    scalars (its expressions, its order), ``p`` at most ``len(alphas)``, the steps the column ran."""
+    b = np.asarray(b, dtype=np.float64)
+    a, bt = np.asarray(alphas, dtype=np.float64), np.asarray(betas, dtype=np.float64)
+    p = int(p)
+    if not 0 <= p <= len(a):
+        raise ValueError("0 to len(alphas) vectors")
+    V = np.zeros((p, b.size))
+    v_old, v = np.zeros(b.size), (b / bt[0] if p else b)
+    for i in range(p):
+        V[i] = v
+        if i + 1 < p:
+            w = matvec(v) - (bt[i] if i else 0.0) * v_old
+            w = w - a[i] * v
+            v_old, v = v, w / bt[i + 1]
+    return V
+
+
+def lanczos_combine_prefix_host(matvec, V, alphas, betas, G):
+    """Pass 2 of one column from a prefix: ``V`` (``[p, n]``, p >= 1) holds its first p Lanczos vectors, ``G`` is ``[m]`` or
+    ``[m, NC]``.  Returns ``[NC, n]``.  ``prefix_split(m, p)``: the terms it assigns to the stream come from ``V``, then the
+    recurrence of ``lanczos_combine_host`` runs from ``V[p - 2]``, ``V[p - 1]`` - its expressions in its order, every
+    term added in ascending i, so the result is ``lanczos_combine_host``'s bit for bit."""
+    V = np.atleast_2d(np.asarray(V, dtype=np.float64))
+    g = np.asarray(G, dtype=np.float64)
+    g = g[:, None] if g.ndim == 1 else g
+    m, nc = g.shape
+    p = len(V)
+    q = np.zeros((nc, V.shape[1]))
+    stream, products = prefix_split(m, p)
+    for i in range(stream):
+        q += g[i][:, None] * V[i][None, :]
+    if m <= p:
+        return q
+    a, bt = np.asarray(alphas, dtype=np.float64), np.asarray(betas, dtype=np.float64)
+    v_old, v = (V[p - 2] if p >= 2 else np.zeros(V.shape[1])), V[p - 1]
+    for i in range(p - 1, m):
+        q += g[i][:, None] * v[None, :]
+        if i + 1 < m:
+            w = matvec(v) - (bt[i] if i else 0.0) * v_old
+            w = w - a[i] * v
+            v_old, v = v, w / bt[i + 1]
+    return q
+
+
 def lanczos_filter_host(matvec, B, shifts, weights, rtol, atol, maxiter, sign=1.0):
     """``(q[K, n], scalars)`` with ``q_r = sum_j Re(weights[j] x_{j,r})``, ``x_{j,r}`` the MINRES iterate of
     ``sign*(z_j I - H) x = B[r]`` at its own stop step; ``scalars`` is pass 1's result.  A shift still live at the step
@@ -277,7 +350,9 @@ class LanczosRun:
     a shift of column r was still live there), ``groups`` (the column ranges of the calls of <= 8) and
     ``products_pass1[g]`` (block products of group g).  ``combine(G)`` is pass 2.  After ``lanczos_run(keepBasis=True)``
     ``basis_kept[g]`` tells whether group g's Lanczos vectors stayed in device memory, ``basis_bytes`` what they hold and
-    ``release()`` gives them back; ``combine`` then streams over them instead of repeating the products."""
+    ``release()`` gives them back; ``combine`` then streams over them instead of repeating the products.  With
+    ``keepPrefix=True`` a group may hold only its first ``basis_vectors[g]`` vectors (``basis_kept[g]`` is then False);
+    ``combine`` streams over those and repeats the products of the rest."""
 
     def __init__(self, H, B, shifts, sign):
         self.H, self.B, self.shifts, self.sign = H, list(B), list(shifts), sign
@@ -290,8 +365,14 @@ class LanczosRun:
         return all(i == 0 for i in self.info)
 
     @property
+    def basis_vectors(self):
+        """Lanczos vectors held per group: those of its longest column, 0 without a basis."""
+        return [int(self._basis_info(g)[0]) if h is not None else 0 for g, h in enumerate(self._bases)]
+
+    @property
     def basis_kept(self):
-        return [h is not None for h in self._bases]
+        """Per group: the whole basis is held (a prefix does not count)."""
+        return [h is not None and v >= p for h, v, p in zip(self._bases, self.basis_vectors, self.products_pass1)]
 
     def _basis_info(self, g):
         from . import _lib
@@ -314,7 +395,9 @@ class LanczosRun:
         imaginary one); wider: a list of NC ``HipVector`` per column.  ``products_pass2[g]`` then holds the block products
         of group g: its largest ``m_r`` minus one - or 0 where the group's basis was kept: those groups are served by one
         stream over the stored vectors, any number of times, with NC up to 8 per call (wider tables are split).  A group
-        without a basis takes the product pass, which serves NC = 1 or 2 (``ValueError`` otherwise)."""
+        that holds a prefix of p vectors is served the same way and adds ``prefix_split(mmax, p)[1]`` products per call
+        of the split.  A group without a basis takes the product pass, which serves NC = 1 or 2 (``ValueError``
+        otherwise)."""
         from . import _lib
         from .hip_vector import HipComplexVector, _ptr_table
         kept = bool(self._bases) and all(h is not None for h in self._bases)
@@ -326,18 +409,29 @@ class LanczosRun:
             k = hi - lo
             m = (C.c_int * k)(*[len(tabs[r]) for r in range(lo, hi)])
             if g < len(self._bases) and self._bases[g] is not None:
+                al = [np.ascontiguousarray(self.scalars[r].alphas, dtype=np.float64) for r in range(lo, hi)]
                 be = [np.ascontiguousarray(self.scalars[r].betas, dtype=np.float64) for r in range(lo, hi)]
+                pa = (dp * k)(*[a.ctypes.data_as(dp) for a in al])
                 pb = (dp * k)(*[b.ctypes.data_as(dp) for b in be])
                 cols = [[None] * nc for _ in range(k)]
+                tail = prefix_split(max(m), self._basis_info(g)[0])[1]      # products per call: 0 from a whole basis
+                products, stats = 0, (C.c_double * 2)()
                 for c0, w in split_combinations(nc):
                     part = [np.ascontiguousarray(tabs[r][:, c0:c0 + w]) for r in range(lo, hi)]
                     pg = (dp * k)(*[t.ctypes.data_as(dp) for t in part])
                     bufs = [ctx.alloc(n) for _ in range(k * w)]
                     qt, keep2 = _ptr_table(bufs)
-                    _lib.call("hipeig_lanczos_basis_combine", ctx.handle, self._bases[g], k, m, pb, w, pg, qt)
+                    if tail:
+                        _lib.call("hipeig_lanczos_basis_combine_tail", ctx.handle, self.H.handle, self._bases[g], k, m, pa, pb,
+                                  w, pg, qt, stats)
+                        if int(stats[0]) != tail:
+                            raise RuntimeError(f"the tail made {int(stats[0])} products, not {tail}")
+                        products += tail
+                    else:
+                        _lib.call("hipeig_lanczos_basis_combine", ctx.handle, self._bases[g], k, m, pb, w, pg, qt)
                     for j in range(k):
                         cols[j][c0:c0 + w] = [self.B[lo + j]._new(bufs[j * w + c]) for c in range(w)]
-                self.products_pass2.append(0)
+                self.products_pass2.append(products)
                 for j in range(k):
                     out.append(cols[j][0] if nc == 1 else HipComplexVector(*cols[j]) if nc == 2 else cols[j])
                 continue
@@ -387,7 +481,7 @@ def _default_basis_budget(ctx, basisBytes, held):
     return basis_budget(ctx.device_info()["hbm_free"], info[5])
 
 
-def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None):
+def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None, keepPrefix=False):
     """Pass 1 on the device (``hipeig_lanczos_block_scalars``) for the real ``HipVector``s ``B`` and up to 32 ``shifts``
     (real or complex) of ``sign*(z I - H)``, ``sign = -1`` with ``reverseGF``: a ``LanczosRun``.  More than 8 columns are
     grouped into calls of 8, each in lock step on block products.  Tolerances and the step limit come from
@@ -395,9 +489,13 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None)
 
     ``keepBasis``: every group keeps its Lanczos vectors in device memory (``hipeig_lanczos_block_scalars_keep``, the same
     scalars) as long as the byte budget allows - ``basisBytes`` for the whole run, by default ``basis_budget`` of the free
-    device memory.  A group whose basis does not fit finishes as a plain pass 1; ``run.basis_kept`` tells."""
+    device memory.  A group whose basis does not fit finishes as a plain pass 1; ``run.basis_kept`` tells.
+
+    ``keepPrefix`` (with ``keepBasis``): such a group keeps the vectors that fit instead
+    (``hipeig_lanczos_block_scalars_prefix``, again the same scalars); ``run.basis_vectors`` tells how many."""
     from . import _lib
     from .hip_vector import _ptr_table
+    keepPrefix = _checked_prefix(keepPrefix, keepBasis, "lanczos_run(keepPrefix=True)")
     B = _checked_inputs(H, B, "lanczos_run")
     if basisBytes is not None and int(basisBytes) < 0:
         raise ValueError("basisBytes must not be negative")
@@ -427,7 +525,7 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None)
         if keepBasis:
             basis = C.c_void_p()
             budget = _default_basis_budget(ctx, basisBytes, run.basis_bytes)
-            _lib.call("hipeig_lanczos_block_scalars_keep", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
+            _lib.call("hipeig_lanczos_block_scalars_prefix" if keepPrefix else "hipeig_lanczos_block_scalars_keep", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
                       alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats, budget, C.byref(basis))
             run._bases.append(C.c_void_p(basis.value) if basis.value else None)
         else:
@@ -445,17 +543,19 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None)
     return run
 
 
-def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", basisBytes=None):
+def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", basisBytes=None, prefix=False):
     """``[q_r]`` (``HipVector``) with ``q_r = sum_j Re(weights[j] x_{j,r})``, ``x_{j,r}`` the MINRES iterate of
     ``sign*(z_j I - H) x = B[r]`` at its own stop step - FEAST's filtered vectors with ``weights[j] = -0.5 w_j r phase_j`` -
     from two Lanczos passes on the device, no solution ever formed.  Every ``b.last_solve_stats`` = ``{"iterations":
     [per shift], "estimates": [|tau_j|], "products": block products of both passes of b's group, "products_pass1",
-    "products_pass2", "basis": "kept" | "recomputed"}``.  A shift still live at the step limit raises ``UserWarning`` as
+    "products_pass2", "basis": "kept" | "prefix" | "recomputed", "basis_vectors": vectors of the group held for pass 2}``.  A shift still live at the step limit raises ``UserWarning`` as
     every other solver does.
 
     ``basis="keep"``: group by group - pass 1 with its vectors kept, coefficients, one stream over the vectors, release - so
     at most one group's basis is alive at a time and every group has the whole budget (``basisBytes``, default
-    ``basis_budget``).  A group whose basis does not fit is served by the product pass and reports ``"recomputed"``."""
+    ``basis_budget``).  A group whose basis does not fit is served by the product pass and reports ``"recomputed"`` - or,
+    with ``prefix=True``, keeps the vectors that fit, repeats only the products behind them and reports ``"prefix"``."""
+    prefix = _checked_prefix(prefix, basis == "keep", "lanczos_filter(prefix=True)")
     B = _checked_inputs(H, B, "lanczos_filter")
     _checked_basis_mode(basis, "basis")
     if len(np.asarray(weights).reshape(-1)) != len(np.asarray(shifts).reshape(-1)):
@@ -466,11 +566,12 @@ def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", ba
         spans = [(0, len(B))]                                       # every group's pass 1 first, then every pass 2
     q, converged = [], True
     for first, (lo, hi) in enumerate(spans):
-        run = lanczos_run(H, B[lo:hi], shifts, reverseGF=reverseGF, keepBasis=basis == "keep", basisBytes=basisBytes)
+        run = lanczos_run(H, B[lo:hi], shifts, reverseGF=reverseGF, keepBasis=basis == "keep", basisBytes=basisBytes,
+                          keepPrefix=prefix)
         try:
             G = filter_coefficients(run.scalars, run.shifts, weights, run.sign)
             part = run.combine(G) if run.converged else None
-            kept = run.basis_kept
+            kept, held = run.basis_kept, run.basis_vectors
         finally:
             run.release()
         converged = converged and part is not None
@@ -482,7 +583,8 @@ def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", ba
                 b.last_solve_stats = {"iterations": [int(i) for i in run.scalars[r].iterations],
                                       "estimates": [float(e) for e in run.scalars[r].estimates],
                                       "products": p1 + p2, "products_pass1": p1, "products_pass2": p2, "group": first + g,
-                                      "basis": "kept" if kept[g] else "recomputed"}
+                                      "basis": "kept" if kept[g] else "prefix" if held[g] else "recomputed",
+                                      "basis_vectors": held[g]}
                 if part is not None:
                     part[r].last_solve_stats = b.last_solve_stats
         if part is not None:

@@ -366,8 +366,28 @@ int hipeig_lanczos_block_scalars_keep(hipeig_ctx* ctx, hipeig_csr* A, double sig
  * bit for bit.                                                                                                        */
 int hipeig_lanczos_basis_combine(hipeig_ctx* ctx, const hipeig_lanczos_basis* basis, int k, const int* m,
                                  const double* const* betas, int nc, const double* const* G, double* const* q);
+/* Keep mode that holds on to a PREFIX (lanczos_filter.py, lanczos_run(keepBasis=True, keepPrefix=True)): the arguments and,
+ * while segments can be had, the behaviour of hipeig_lanczos_block_scalars_keep.  When the next segment is refused (budget
+ * or device memory) the segments held stay and are written to their last slot - p = segments * slots vectors - and from
+ * step p - 1 on the new vector goes to the ring of three; steps p - 1 and p read their operands from the slots, so the
+ * kernels, operands and scalars are the plain run's (bit for bit with the row-owner sweep).  The basis then holds
+ * min(steps of column j, p) vectors per column.  A run that stops before p ends as a whole basis; *basis is NULL only when
+ * not even the first segment fits.  The workspace of the tail pass (nc <= 2) is reserved before the first segment.      */
+int hipeig_lanczos_block_scalars_prefix(hipeig_ctx* ctx, hipeig_csr* A, double sign, int k, const double* const* b,
+                                        int nshift, const double* zr, const double* zi, double rtol, double atol,
+                                        int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
+                                        int* info, double* out_stats, int64_t basis_bytes, hipeig_lanczos_basis** basis);
+/* PASS 2 from a prefix (lanczos_filter.py, LanczosRun.combine): the sums of hipeig_lanczos_block_combine for nc = 1, 2, 4
+ * or 8 from a basis that holds p vectors.  With mmax = max_j m[j] <= p it is hipeig_lanczos_basis_combine.  Otherwise the
+ * stream takes the terms i < p - 1, r_{p-2} and r_{p-1} are copied out of their slots (the basis is never written) and
+ * the recurrence of pass 2 runs from step p - 1: out_stats[0] (may be NULL) = mmax - p block products instead of mmax - 1.
+ * m[j] at most the steps column j ran; alphas[j], betas[j]: pass 1's.  Every element meets the operations of the product
+ * pass in its order: with the row-owner sweep the result equals it bit for bit.                                        */
+int hipeig_lanczos_basis_combine_tail(hipeig_ctx* ctx, hipeig_csr* A, const hipeig_lanczos_basis* basis, int k,
+                                      const int* m, const double* const* alphas, const double* const* betas, int nc,
+                                      const double* const* G, double* const* q, double* out_stats);
 /* What a kept basis holds (lanczos_filter.py, LanczosRun.basis_bytes and default_basis_budget): info[0] vectors kept (the
- * largest column's), [1] bytes of its segments, [2] interleave width K, [3] rows, [4] columns, [5] bytes of released
+ * largest column's; behind a prefix at most its p), [1] bytes of its segments, [2] interleave width K, [3] rows, [4] columns, [5] bytes of released
  * segments the context would hand out again, [6] segments, [7] slots per segment.  basis may be NULL: only [5] is set. */
 int hipeig_lanczos_basis_info(hipeig_ctx* ctx, const hipeig_lanczos_basis* basis, int64_t info[8]);
 /* Give a kept basis's segments back to the context for reuse (lanczos_filter.py, LanczosRun.release); basis may be NULL.

@@ -5,7 +5,9 @@ subspace vectors, 16 Legendre nodes = 8 contour points, window [-0.21, 0.21], in
 ``linearSolver="minres_shifted"`` (one shared-Lanczos solve per subspace vector for all 8 points) and with
 ``linearSolver="lanczos_filter"`` (mode ``filter``: the filtered vectors from two Lanczos passes, 8 vectors in lock step
 on block products, no per-shift vector) and with the same plus ``"lanczosBasis": "keep"`` (mode ``basis``: pass 1 keeps its
-vectors in device memory and pass 2 is one stream over them), the modes alternating.  One JSON line per run as soon as it
+vectors in device memory and pass 2 is one stream over them) and with that plus ``"lanczosBasisPrefix": True`` (mode
+``prefix``: a basis that outgrows the byte budget keeps the vectors that fit, and pass 2 repeats only the products behind
+them), the modes alternating.  One JSON line per run as soon as it
 is measured; the first line describes the device.
 
 Then the per-phase split of one shared solve (``--phases``, default on): the whole 8-shift solve of the first subspace
@@ -18,7 +20,7 @@ mode: one 8-column run with the keeping pass 1 and the combination from the kept
 per group and its TB/s against the byte model 8 n K m + 8 n K NC (m slots read, NC outputs written), for NC = 1, 2 and 8 -
 and the bytes the basis holds.
 
-    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted,filter,basis] >> profiles/NN_shifted_feast.jsonl
+    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted,filter,basis,prefix] >> profiles/NN_shifted_feast.jsonl
 
 ``--cpu``: instead, the NumPy twins on the host generator's operator (small N): products per shift of the shared-Lanczos
 solver, and the two-pass filter's products and its difference from the former's sum; no timing claims;
@@ -50,7 +52,7 @@ def main():
     ap.add_argument("--cols", type=int, default=4, help="arnoldiColumnsPerPass of the gcrotmk mode")
     ap.add_argument("--phases", type=int, default=1)
     ap.add_argument("--probe-steps", type=int, default=200)
-    ap.add_argument("--basis-bytes", type=int, default=None, help="byte budget of the basis mode (default: the library's rule)")
+    ap.add_argument("--basis-bytes", type=int, default=None, help="byte budget of the basis and prefix modes (default: the library's rule)")
     ap.add_argument("--label", default="")
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--cpu-gcrotmk", action="store_true", help="with --cpu: also count SciPy gcrotmk's products per point")
@@ -107,9 +109,11 @@ def main():
            "shifted": {"linearSolver": "minres_shifted", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7},
            "filter": {"linearSolver": "lanczos_filter", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7},
            "basis": {"linearSolver": "lanczos_filter", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7}}
-    extra = {"basis": {"lanczosBasis": "keep"}}
+    lsa["prefix"] = dict(lsa["basis"])
+    extra = {"basis": {"lanczosBasis": "keep"}, "prefix": {"lanczosBasis": "keep", "lanczosBasisPrefix": True}}
     if a.basis_bytes is not None:
         extra["basis"]["lanczosBasisBytes"] = a.basis_bytes
+        extra["prefix"]["lanczosBasisBytes"] = a.basis_bytes
     Y0 = la.qr(rng.standard_normal((N, m0)), mode="economic")[0]
     ctx = ea.HipContext.default()
     print(json.dumps({"device": ctx.device_info()["name"], "N": N, "m0": m0, "contour_points": a.nc // 2, "reps": a.reps,
@@ -150,10 +154,11 @@ def main():
                             "iterations_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk)),
                                                               int(max(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk))]
                                                              for kk in range(a.nc // 2)]})
-            elif mode in ("filter", "basis"):
+            elif mode in ("filter", "basis", "prefix"):
                 rec = st["lanczosFilter"][0]
                 row.update({"runs": rec["runs"], "block_products_pass1": rec["products_pass1"],
                             "block_products_pass2": rec["products_pass2"], "basis": rec["basis"],
+                            "basis_vectors": rec.get("basis_vectors"),
                             "steps_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["steps"]) if k == kk)),
                                                          int(max(i for (k, v), i in zip(rec["pairs"], rec["steps"]) if k == kk))]
                                                         for kk in range(a.nc // 2)]})
