@@ -106,16 +106,9 @@ SIGNATURES = {
     "hipeig_minres_block": [_P, _P, _D, _D, C.c_int, _PP, _PP, _D, C.c_int, _IP, _DP],
     "hipeig_minres_shifts": [_P, _P, _D, C.c_int, _DP, _DP, _P, _PP, _PP, _D, _D, C.c_int, _IP, _DP],
     "hipeig_lanczos_block_scalars": [_P, _P, _D, C.c_int, _PP, C.c_int, _DP, _DP, _D, _D, C.c_int, _DP, _DP, _IP, _DP, _IP,
-                                     _DP],
-    "hipeig_lanczos_block_combine": [_P, _P, C.c_int, _PP, _IP, C.POINTER(_DP), C.POINTER(_DP), C.c_int, C.POINTER(_DP),
-                                     _PP, _DP],
-    "hipeig_lanczos_block_scalars_keep": [_P, _P, _D, C.c_int, _PP, C.c_int, _DP, _DP, _D, _D, C.c_int, _DP, _DP, _IP, _DP,
-                                          _IP, _DP, _I64, _PP],
-    "hipeig_lanczos_basis_combine": [_P, _P, C.c_int, _IP, C.POINTER(_DP), C.c_int, C.POINTER(_DP), _PP],
-    "hipeig_lanczos_block_scalars_prefix": [_P, _P, _D, C.c_int, _PP, C.c_int, _DP, _DP, _D, _D, C.c_int, _DP, _DP, _IP, _DP,
-                                            _IP, _DP, _I64, _PP],
-    "hipeig_lanczos_basis_combine_tail": [_P, _P, _P, C.c_int, _IP, C.POINTER(_DP), C.POINTER(_DP), C.c_int,
-                                          C.POINTER(_DP), _PP, _DP],
+                                     _DP, C.c_int, _I64, _PP],
+    "hipeig_lanczos_combine": [_P, _P, _P, C.c_int, _PP, _IP, C.POINTER(_DP), C.POINTER(_DP), C.c_int, C.POINTER(_DP), _PP,
+                               _DP],
     "hipeig_lanczos_basis_info": [_P, _P, _I64P],
     "hipeig_lanczos_basis_release": [_P, _P],
     "hipeig_csr_set_block_variant": [_P, C.c_int],

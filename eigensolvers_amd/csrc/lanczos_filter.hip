@@ -12,15 +12,15 @@
 // minres_block.hip: every workgroup leaves K partials, the consumer's prologue adds them in a fixed order.  A column that
 // has stopped is masked: its scalars are no longer recorded and its vectors are zeroed (s = 0), never read.
 //
-// Pass 2 (hipeig_lanczos_block_combine), one kernel per step, no reduction: the block sweep's element epilogue does
+// Pass 2 (hipeig_lanczos_combine), one kernel per step, no reduction: the block sweep's element epilogue does
 //   q[c] += G[r][i][c] v_i ;  r_{i+1} = (H r_i)/beta_i - (beta_i/beta_{i-1}) r_{i-1} - (alpha_i/beta_i) r_i   written over r_{i-1}
 // (v_{i+1} = (H v_i - alpha_i v_i - beta_i v_{i-1}) / beta_{i+1} on pass 1's un-normalised vectors, v_i = r_i / beta_i)
 // from the scalar tables uploaded once; column r stops after its own m_r terms; the last term needs no product.
 //
-// Keep mode (hipeig_lanczos_block_scalars_keep): pass 1 leaves every r_k in a slot of a basis in device memory instead of
-// a ring of three, and pass 2 (hipeig_lanczos_basis_combine) is one stream over the slots - see "kept basis" below.
-// Prefix mode (hipeig_lanczos_block_scalars_prefix): a basis that outgrows its byte budget keeps the first p vectors, and
-// pass 2 (hipeig_lanczos_basis_combine_tail) is the stream for the terms i < p - 1 plus the recurrence from step p - 1.
+// Keep mode (basis_mode 1): pass 1 leaves every r_k in a slot of a basis in device memory instead of a ring of three, and
+// pass 2 is one stream over the slots - see "kept basis" below.  Prefix mode (basis_mode 2): a basis that outgrows its
+// byte budget keeps the first p vectors, and pass 2 is the stream for the terms i < p - 1 plus the recurrence from step
+// p - 1.  The three are one host path with a plan - see "pass 2, host side".
 #include <limits.h>
 #include <math.h>
 #include "spmm_device.h"
@@ -228,7 +228,7 @@ lf_scalar_kernel(LfState* __restrict__ S, LfShifts a, const double* __restrict__
 // alpha_i / beta_i [K], G[i][K][NC] - formed on the host with the divisions pass 1's kernels make.
 #define LF_TAB(K, NC) ((K) * (3 + (NC)))
 
-// Doubles of workspace the tail pass of a prefix basis takes at most (lf_combine_tail_impl): the state record's area, the
+// Doubles of workspace pass 2 takes at most (lf_pass2_impl; a prefix basis comes closest): the state record's area, the
 // stream's and the product steps' tables for `steps` steps in all, two work vectors and NC packed combinations.
 static int64_t lf_tail_doubles(int K, int NC, int64_t steps, int64_t nb) {
   const int64_t tab_d = (steps * (LF_TAB(K, NC) + K * (1 + NC) + 1) + 3 * K + 31) & ~(int64_t)31;
@@ -257,7 +257,7 @@ struct LfCombineEpilogue {
   }
 };
 
-// NC <= 2 serves the product pass (hipeig_lanczos_block_combine); the tail of a prefix basis takes NC up to 8 - the
+// NC <= 2 serves a pass 2 without a basis; the product steps behind a prefix basis take NC up to 8 - the
 // epilogue then holds NC coefficients per thread and makes NC read-modify-writes of Q per element, nothing else changes.
 template <int VARIANT, int K, int NC>
 __global__ void __launch_bounds__(VARIANT == 2 ? BCOO_THREADS : HIPEIG_BLOCK)
@@ -419,8 +419,8 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   const int64_t ld = maxiter;
   const int64_t tabs = ((int64_t)K * (2 * ld + 1) + 31) & ~(int64_t)31;
   int64_t need = LF_HEAD_DOUBLES + tabs + 3 * nb;
-  // a prefix is followed by a tail pass: its workspace (NC <= 2) is taken before the first segment, so that the basis
-  // cannot eat the room of the pass it serves
+  // a prefix is followed by a pass 2 with product steps: its workspace (NC <= 2) is taken before the first segment, so
+  // that the basis cannot eat the room of the pass it serves
   if (keep && prefix && lf_tail_doubles(K, 2, maxiter, nb) > need) need = lf_tail_doubles(K, 2, maxiter, nb);
   if (lf_reserve(c, need)) return 1;
   if (!c->h_lf_state) HIPEIG_CHECK(hipHostMalloc((void**)&c->h_lf_state, sizeof(LfState), hipHostMallocDefault));
@@ -582,10 +582,15 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   return 0;
 }
 
-static int lf_scalars_entry(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b, int nshift,
-                            const double* zr, const double* zi, double rtol, double atol, int maxiter, double* alphas,
-                            double* betas, int* iterations, double* estimates, int* info, double* out_stats, int64_t budget,
-                            hipeig_lanczos_basis** keep, int prefix) {
+extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
+                                            int nshift, const double* zr, const double* zi, double rtol, double atol,
+                                            int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
+                                            int* info, double* out_stats, int basis_mode, int64_t basis_bytes,
+                                            hipeig_lanczos_basis** basis) {
+  HIPEIG_REQUIRE(basis_mode >= 0 && basis_mode <= 2, "basis mode: 0 none, 1 keep, 2 keep a prefix");
+  HIPEIG_REQUIRE(basis_mode == 0 || basis != nullptr, "null argument");
+  if (basis) *basis = nullptr;
+  HIPEIG_REQUIRE(basis_mode == 0 || basis_bytes >= 0, "negative byte budget");
   HIPEIG_REQUIRE(b && zr && zi && alphas && betas && iterations && estimates && info, "null argument");
   HIPEIG_REQUIRE(k >= 1 && k <= BCOO_KMAX, "1 to 8 right-hand sides per call");
   HIPEIG_REQUIRE(nshift >= 1 && nshift <= LF_MAX_SHIFTS, "1 to 32 shifts per run");
@@ -601,44 +606,13 @@ static int lf_scalars_entry(hipeig_ctx* c, hipeig_csr* A, double sign, int k, co
   }
   if (out_stats) memset(out_stats, 0, (size_t)(1 + k) * sizeof(double));
   if (A->nrows == 0) return 0;
+  hipeig_lanczos_basis** keep = basis_mode ? basis : nullptr;
+  const int prefix = basis_mode == 2;
   if (lf_width(k) == 4)
     return lf_scalars_impl<4>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                              out_stats, budget, keep, prefix);
+                              out_stats, basis_bytes, keep, prefix);
   return lf_scalars_impl<8>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                            out_stats, budget, keep, prefix);
-}
-
-extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
-                                            int nshift, const double* zr, const double* zi, double rtol, double atol,
-                                            int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
-                                            int* info, double* out_stats) {
-  return lf_scalars_entry(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                          out_stats, 0, nullptr, 0);
-}
-
-extern "C" int hipeig_lanczos_block_scalars_keep(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
-                                                 int nshift, const double* zr, const double* zi, double rtol, double atol,
-                                                 int maxiter, double* alphas, double* betas, int* iterations,
-                                                 double* estimates, int* info, double* out_stats, int64_t basis_bytes,
-                                                 hipeig_lanczos_basis** basis) {
-  HIPEIG_REQUIRE(basis != nullptr, "null argument");
-  *basis = nullptr;
-  HIPEIG_REQUIRE(basis_bytes >= 0, "negative byte budget");
-  return lf_scalars_entry(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                          out_stats, basis_bytes, basis, 0);
-}
-
-// Keep mode that holds on to a prefix: see lf_scalars_impl.
-extern "C" int hipeig_lanczos_block_scalars_prefix(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b,
-                                                   int nshift, const double* zr, const double* zi, double rtol, double atol,
-                                                   int maxiter, double* alphas, double* betas, int* iterations,
-                                                   double* estimates, int* info, double* out_stats, int64_t basis_bytes,
-                                                   hipeig_lanczos_basis** basis) {
-  HIPEIG_REQUIRE(basis != nullptr, "null argument");
-  *basis = nullptr;
-  HIPEIG_REQUIRE(basis_bytes >= 0, "negative byte budget");
-  return lf_scalars_entry(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                          out_stats, basis_bytes, basis, 1);
+                            out_stats, basis_bytes, keep, prefix);
 }
 
 // Table records of the product steps `first` .. m[j] - 1 of every column, record i at t0 + (i - first) * LF_TAB.
@@ -701,67 +675,6 @@ static int lf_unpack_combinations(hipeig_ctx* c, int64_t n, int k, const double*
     if (hipeig_block_unpack(c, K, n, k, Q + (int64_t)cc * nb, part)) return 1;
   }
   return 0;
-}
-
-template <int K, int NC>
-static int lf_combine_impl(hipeig_ctx* c, hipeig_csr* A, int k, const double* const* b, const int* m,
-                           const double* const* alphas, const double* const* betas, const double* const* G,
-                           double* const* q, double* out_stats) {
-  const int64_t n = A->nrows;
-  int mmax = 0;
-  for (int j = 0; j < k; ++j) mmax = m[j] > mmax ? m[j] : mmax;
-  if (mmax == 0) {
-    for (int j = 0; j < k * NC; ++j) if (hipeig_vec_fill(c, q[j], n, 0.0)) return 1;
-    return 0;
-  }
-  // device tables: mmax records of LF_TAB doubles, then m[K] as ints
-  const int64_t nb = ((n * K + 31) & ~(int64_t)31);
-  const int64_t tab_d = ((int64_t)mmax * LF_TAB(K, NC) + 2 * K + 31) & ~(int64_t)31;
-  if (lf_reserve(c, LF_HEAD_DOUBLES + tab_d + (2 + NC) * nb)) return 1;
-  double* d_tab = c->lf_ws + LF_HEAD_DOUBLES;
-  int* d_m = reinterpret_cast<int*>(d_tab + (int64_t)mmax * LF_TAB(K, NC));
-  double* Vb[2] = {c->lf_ws + LF_HEAD_DOUBLES + tab_d, c->lf_ws + LF_HEAD_DOUBLES + tab_d + nb};
-  double* Q = c->lf_ws + LF_HEAD_DOUBLES + tab_d + 2 * nb;
-  double* h_tab = (double*)calloc((size_t)tab_d, sizeof(double));
-  HIPEIG_REQUIRE(h_tab != nullptr, "out of host memory");
-  int* h_m = reinterpret_cast<int*>(h_tab + (int64_t)mmax * LF_TAB(K, NC));
-  for (int j = 0; j < K; ++j) h_m[j] = j < k ? m[j] : 0;
-  lf_fill_product_tab<K, NC>(h_tab, 0, k, m, alphas, betas, G);
-  hipError_t e = hipMemcpyAsync(d_tab, h_tab, (size_t)tab_d * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  free(h_tab);
-  HIPEIG_CHECK(e);
-  if (hipeig_block_pack(c, K, n, k, b, Vb[0])) return 1;
-  HIPEIG_CHECK(hipMemsetAsync(Vb[1], 0, (size_t)nb * (1 + NC) * sizeof(double), c->stream));
-  if (lf_enqueue_products<K, NC>(c, A, d_tab, d_m, 0, mmax, Vb, Q, nb)) return 1;
-  if (lf_unpack_combinations<K, NC>(c, n, k, Q, nb, q)) return 1;
-  if (hipeig_sync_checked(c)) return 4;
-  if (out_stats) out_stats[0] = mmax - 1;
-  return 0;
-}
-
-extern "C" int hipeig_lanczos_block_combine(hipeig_ctx* c, hipeig_csr* A, int k, const double* const* b, const int* m,
-                                            const double* const* alphas, const double* const* betas, int nc,
-                                            const double* const* G, double* const* q, double* out_stats) {
-  HIPEIG_REQUIRE(b && m && alphas && betas && G && q, "null argument");
-  HIPEIG_REQUIRE(k >= 1 && k <= BCOO_KMAX, "1 to 8 right-hand sides per call");
-  HIPEIG_REQUIRE(nc == 1 || nc == 2, "one or two combinations per column");
-  HIPEIG_REQUIRE(!c->collectives, "the Lanczos filter runs on whole vectors (no row partition)");
-  HIPEIG_REQUIRE(A->nrows == A->ncols, "the Lanczos run needs a square operator");
-  for (int j = 0; j < k; ++j) {
-    HIPEIG_REQUIRE(m[j] >= 0, "negative number of terms");
-    HIPEIG_REQUIRE(b[j] != nullptr && (m[j] == 0 || (alphas[j] && betas[j] && G[j])), "null column argument");
-    for (int cc = 0; cc < nc; ++cc) HIPEIG_REQUIRE(q[j * nc + cc] != nullptr && q[j * nc + cc] != b[j], "q must not be null or alias b");
-    for (int i = 1; i < m[j]; ++i) HIPEIG_REQUIRE(betas[j][i] > 0.0, "a Lanczos vector past a breakdown was asked for");
-    HIPEIG_REQUIRE(m[j] == 0 || betas[j][0] > 0.0, "terms asked for a zero right-hand side");
-  }
-  if (out_stats) out_stats[0] = 0.0;
-  if (A->nrows == 0) return 0;
-  const int K = lf_width(k);
-  if (K == 4) return nc == 1 ? lf_combine_impl<4, 1>(c, A, k, b, m, alphas, betas, G, q, out_stats)
-                             : lf_combine_impl<4, 2>(c, A, k, b, m, alphas, betas, G, q, out_stats);
-  return nc == 1 ? lf_combine_impl<8, 1>(c, A, k, b, m, alphas, betas, G, q, out_stats)
-                 : lf_combine_impl<8, 2>(c, A, k, b, m, alphas, betas, G, q, out_stats);
 }
 
 // ---- pass 2 from a kept basis ------------------------------------------------------------------------------------------
@@ -834,166 +747,144 @@ lf_basis_combine_kernel(int64_t n2, int mmax, const double* __restrict__ tab, co
   }
 }
 
+// ---- pass 2, host side -------------------------------------------------------------------------------------------------
+// One path with a plan (prefix_split in lanczos_filter.py states it): the terms i < stream come from the basis's slots in
+// one stream (columns masked by min(m_j, stream)) that leaves Q packed in the workspace; the recurrence takes over at step
+// first = stream on two work vectors and makes a product per step up to mmax - 2 (columns masked by m_j), then the last term.
+//   no basis                stream = 0        r_0 = packed b, r_{-1} = zeros                          mmax - 1 products
+//   basis holds p >= mmax   stream = mmax     -                                                       none
+//   basis holds p <  mmax   stream = p - 1    r_{p-1}, r_{p-2} copied from their slots (zeros, p = 1)  mmax - p products
+// The basis is never written: it serves any number of calls.  Every element meets the mul_rn / fma sequence of the
+// product steps in ascending i (the stream's accumulators start from 0, as Q does without a stream), so with the
+// row-owner sweep the three situations agree bit for bit.
+struct LfPlan {
+  int mmax, stream;
+  int64_t o_slots, o_prod, o_m, tab_d;                         // the table's parts, in doubles: see lf_fill_pass2_tab
+  bool recurs() const { return stream < mmax; }
+  int products() const { return recurs() ? mmax - 1 - stream : 0; }
+};
+
 template <int K, int NC>
-static int lf_basis_combine_impl(hipeig_ctx* c, const hipeig_lanczos_basis* B, int k, const int* m,
-                                 const double* const* betas, const double* const* G, double* const* q) {
-  const int64_t n = B->n, nb = B->nb;
-  int mmax = 0;
-  for (int j = 0; j < k; ++j) mmax = m[j] > mmax ? m[j] : mmax;
-  if (mmax == 0) {
+static LfPlan lf_plan(const hipeig_lanczos_basis* B, int k, const int* m) {
+  LfPlan P{};
+  int p = 0;                                                  // vectors the basis holds for its longest column
+  for (int j = 0; j < k; ++j) {
+    P.mmax = m[j] > P.mmax ? m[j] : P.mmax;
+    if (B) p = B->steps[j] > p ? B->steps[j] : p;
+  }
+  P.stream = !B ? 0 : p >= P.mmax ? P.mmax : p - 1;
+  P.o_slots = (int64_t)P.stream * LF_BC_TAB(K, NC);
+  P.o_prod = P.o_slots + P.stream;
+  P.o_m = P.o_prod + (P.recurs() ? (int64_t)(P.mmax - P.stream) * LF_TAB(K, NC) : 0);
+  P.tab_d = (P.o_m + K + 31) & ~(int64_t)31;
+  return P;
+}
+
+// Pass 2's table: `stream` records of LF_BC_TAB doubles, `stream` slot pointers, the records of the steps stream ..
+// mmax - 1 (lf_fill_product_tab), then min(m_j, stream) [K] and m_j [K] as ints.  h_tab comes zeroed.
+template <int K, int NC>
+static void lf_fill_pass2_tab(double* h_tab, const LfPlan& P, const hipeig_lanczos_basis* B, int k, const int* m,
+                              const double* const* alphas, const double* const* betas, const double* const* G) {
+  static_assert(sizeof(double*) == sizeof(double), "slot pointers are stored in the table's doubles");
+  const double** h_slots = reinterpret_cast<const double**>(h_tab + P.o_slots);
+  int* h_ms = reinterpret_cast<int*>(h_tab + P.o_m);
+  int* h_m = h_ms + K;
+  for (int i = 0; i < P.stream; ++i) h_slots[i] = lf_slot(B, i);
+  for (int j = 0; j < K; ++j) {
+    h_m[j] = j < k ? m[j] : 0;
+    h_ms[j] = h_m[j] < P.stream ? h_m[j] : P.stream;
+    for (int i = 0; i < h_ms[j]; ++i) {
+      double* t = h_tab + (int64_t)i * LF_BC_TAB(K, NC);
+      t[j] = 1.0 / betas[j][i];                              // LfCol::s, as lf_fill_product_tab
+      for (int cc = 0; cc < NC; ++cc) t[K + j * NC + cc] = G[j][(size_t)i * NC + cc];
+    }
+  }
+  if (P.recurs()) lf_fill_product_tab<K, NC>(h_tab + P.o_prod, P.stream, k, m, alphas, betas, G);
+}
+
+template <int K, int NC>
+static int lf_pass2_impl(hipeig_ctx* c, hipeig_csr* A, const hipeig_lanczos_basis* B, int k, const double* const* b,
+                         const int* m, const double* const* alphas, const double* const* betas, const double* const* G,
+                         double* const* q, double* out_stats) {
+  const int64_t n = A->nrows;
+  const int64_t nb = ((n * K + 31) & ~(int64_t)31);
+  const LfPlan P = lf_plan<K, NC>(B, k, m);
+  if (P.mmax == 0) {
     for (int j = 0; j < k * NC; ++j) if (hipeig_vec_fill(c, q[j], n, 0.0)) return 1;
     return 0;
   }
-  // device tables: mmax records of LF_BC_TAB doubles, mmax slot pointers, then m[K] as ints
-  constexpr int TW = LF_BC_TAB(K, NC);
-  const int64_t tab_d = ((int64_t)mmax * (TW + 1) + K + 31) & ~(int64_t)31;
-  if (lf_reserve(c, LF_HEAD_DOUBLES + tab_d + NC * nb)) return 1;
+  // the state record's area, the table, the recurrence's two work vectors - none from a whole basis, which may have left
+  // no room for them - and the NC packed combinations
+  const int64_t need = LF_HEAD_DOUBLES + P.tab_d + ((P.recurs() ? 2 : 0) + NC) * nb;
+  HIPEIG_REQUIRE(need <= lf_tail_doubles(K, NC, P.mmax, nb), "tail workspace bound");
+  if (lf_reserve(c, need)) return 1;
   double* d_tab = c->lf_ws + LF_HEAD_DOUBLES;
-  const double** d_slots = reinterpret_cast<const double**>(d_tab + (int64_t)mmax * TW);
-  int* d_m = reinterpret_cast<int*>(d_tab + (int64_t)mmax * (TW + 1));
-  double* Q = c->lf_ws + LF_HEAD_DOUBLES + tab_d;
-  static_assert(sizeof(double*) == sizeof(double), "slot pointers are stored in the table's doubles");
-  double* h_tab = (double*)calloc((size_t)tab_d, sizeof(double));
+  double* Vb[2] = {d_tab + P.tab_d, d_tab + P.tab_d + nb};
+  double* Q = d_tab + P.tab_d + (P.recurs() ? 2 * nb : 0);
+  double* h_tab = (double*)calloc((size_t)P.tab_d, sizeof(double));
   HIPEIG_REQUIRE(h_tab != nullptr, "out of host memory");
-  const double** h_slots = reinterpret_cast<const double**>(h_tab + (int64_t)mmax * TW);
-  int* h_m = reinterpret_cast<int*>(h_tab + (int64_t)mmax * (TW + 1));
-  for (int i = 0; i < mmax; ++i) h_slots[i] = lf_slot(B, i);
-  for (int j = 0; j < K; ++j) {
-    h_m[j] = j < k ? m[j] : 0;
-    for (int i = 0; i < h_m[j]; ++i) {
-      double* t = h_tab + (int64_t)i * TW;
-      t[j] = 1.0 / betas[j][i];                              // LfCol::s, as lf_combine_impl
-      for (int cc = 0; cc < NC; ++cc) t[K + j * NC + cc] = G[j][(size_t)i * NC + cc];
-    }
-  }
-  hipError_t e = hipMemcpyAsync(d_tab, h_tab, (size_t)tab_d * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  lf_fill_pass2_tab<K, NC>(h_tab, P, B, k, m, alphas, betas, G);
+  hipError_t e = hipMemcpyAsync(d_tab, h_tab, (size_t)P.tab_d * sizeof(double), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   free(h_tab);
   HIPEIG_CHECK(e);
-  const int64_t n2 = n * (K / 2);
-  hipLaunchKernelGGL((lf_basis_combine_kernel<K, NC>), dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream, n2, mmax,
-                     (const double*)d_tab, (const double* const*)d_slots, (const int*)d_m, Q, nb);
-  HIPEIG_CHECK(hipGetLastError());
-  if (lf_unpack_combinations<K, NC>(c, n, k, Q, nb, q)) return 1;
-  if (hipeig_sync_checked(c)) return 4;
-  return 0;
-}
-
-// ---- pass 2 from a prefix ------------------------------------------------------------------------------------------------
-// The basis holds v_0 .. v_{p-1} and the largest column wants mmax > p terms.  The terms i < p - 1 come from the stream
-// (columns masked by min(m_j, p - 1)), which leaves Q packed in the workspace; r_{p-2} and r_{p-1} are copied from their
-// slots into the two work vectors - the basis is never written, it serves any number of calls - and the product loop of
-// lf_combine_impl takes over at step p - 1: mmax - p products, then the last term.  Every element meets the mul_rn / fma
-// sequence of the product pass in ascending i (the stream's accumulator starts from 0 as the product pass's Q does), so
-// with the row-owner sweep the result is the product pass's and a whole basis's, bit for bit.
-template <int K, int NC>
-static int lf_combine_tail_impl(hipeig_ctx* c, hipeig_csr* A, const hipeig_lanczos_basis* B, int k, const int* m,
-                                const double* const* alphas, const double* const* betas, const double* const* G,
-                                double* const* q, int p, int mmax) {
-  const int64_t n = B->n, nb = B->nb;
-  constexpr int TW = LF_BC_TAB(K, NC);
-  const int ms = p - 1, first = p - 1;                        // stream terms of the longest column; first product step
-  // device tables: ms stream records, ms slot pointers, mmax - first product records, then both m[K] as ints
-  const int64_t o_slots = (int64_t)ms * TW, o_prod = o_slots + ms, o_m = o_prod + (int64_t)(mmax - first) * LF_TAB(K, NC);
-  const int64_t tab_d = (o_m + 2 * K + 31) & ~(int64_t)31;
-  HIPEIG_REQUIRE(LF_HEAD_DOUBLES + tab_d + (2 + NC) * nb <= lf_tail_doubles(K, NC, mmax, nb), "tail workspace bound");
-  if (lf_reserve(c, lf_tail_doubles(K, NC, mmax, nb))) return 1;
-  double* d_tab = c->lf_ws + LF_HEAD_DOUBLES;
-  double* Vb[2] = {d_tab + tab_d, d_tab + tab_d + nb};
-  double* Q = d_tab + tab_d + 2 * nb;
-  double* h_tab = (double*)calloc((size_t)tab_d, sizeof(double));
-  HIPEIG_REQUIRE(h_tab != nullptr, "out of host memory");
-  const double** h_slots = reinterpret_cast<const double**>(h_tab + o_slots);
-  int* h_ms = reinterpret_cast<int*>(h_tab + o_m);
-  int* h_m = h_ms + K;
-  for (int i = 0; i < ms; ++i) h_slots[i] = lf_slot(B, i);
-  for (int j = 0; j < K; ++j) {
-    h_m[j] = j < k ? m[j] : 0;
-    h_ms[j] = h_m[j] < ms ? h_m[j] : ms;
-    for (int i = 0; i < h_ms[j]; ++i) {
-      double* t = h_tab + (int64_t)i * TW;
-      t[j] = 1.0 / betas[j][i];                              // LfCol::s, as lf_combine_impl
-      for (int cc = 0; cc < NC; ++cc) t[K + j * NC + cc] = G[j][(size_t)i * NC + cc];
-    }
-  }
-  lf_fill_product_tab<K, NC>(h_tab + o_prod, first, k, m, alphas, betas, G);
-  hipError_t e = hipMemcpyAsync(d_tab, h_tab, (size_t)tab_d * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  free(h_tab);
-  HIPEIG_CHECK(e);
-  const int* d_ms = reinterpret_cast<const int*>(d_tab + o_m);
-  if (ms > 0)
+  const int* d_ms = reinterpret_cast<const int*>(d_tab + P.o_m);
+  if (P.stream > 0)
     hipLaunchKernelGGL((lf_basis_combine_kernel<K, NC>), dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream,
-                       n * (K / 2), ms, (const double*)d_tab, reinterpret_cast<const double* const*>(d_tab + o_slots), d_ms, Q,
-                       nb);
-  else
-    HIPEIG_CHECK(hipMemsetAsync(Q, 0, (size_t)nb * NC * sizeof(double), c->stream));
+                       n * (K / 2), P.stream, (const double*)d_tab, reinterpret_cast<const double* const*>(d_tab + P.o_slots),
+                       d_ms, Q, nb);
+  else                                                        // no stream: the recurrence starts at step 0, r_{-1} = Q = 0
+    HIPEIG_CHECK(hipMemsetAsync(Vb[1], 0, (size_t)nb * (1 + NC) * sizeof(double), c->stream));
   HIPEIG_CHECK(hipGetLastError());
-  HIPEIG_CHECK(hipMemcpyAsync(Vb[first & 1], lf_slot(B, first), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  if (first)
-    HIPEIG_CHECK(hipMemcpyAsync(Vb[(first + 1) & 1], lf_slot(B, first - 1), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice,
-                                c->stream));
-  else
-    HIPEIG_CHECK(hipMemsetAsync(Vb[1], 0, (size_t)nb * sizeof(double), c->stream));
-  if (lf_enqueue_products<K, NC>(c, A, d_tab + o_prod, d_ms + K, first, mmax, Vb, Q, nb)) return 1;
+  if (P.recurs()) {
+    const int first = P.stream;
+    if (B)
+      HIPEIG_CHECK(hipMemcpyAsync(Vb[first & 1], lf_slot(B, first), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    else if (hipeig_block_pack(c, K, n, k, b, Vb[0]))
+      return 1;
+    if (first)
+      HIPEIG_CHECK(hipMemcpyAsync(Vb[(first + 1) & 1], lf_slot(B, first - 1), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice,
+                                  c->stream));
+    if (lf_enqueue_products<K, NC>(c, A, d_tab + P.o_prod, d_ms + K, first, P.mmax, Vb, Q, nb)) return 1;
+  }
   if (lf_unpack_combinations<K, NC>(c, n, k, Q, nb, q)) return 1;
   if (hipeig_sync_checked(c)) return 4;
+  if (out_stats) out_stats[0] = P.products();
   return 0;
 }
 
-extern "C" int hipeig_lanczos_basis_combine(hipeig_ctx* c, const hipeig_lanczos_basis* B, int k, const int* m,
-                                            const double* const* betas, int nc, const double* const* G, double* const* q);
-
-extern "C" int hipeig_lanczos_basis_combine_tail(hipeig_ctx* c, hipeig_csr* A, const hipeig_lanczos_basis* B, int k,
-                                                 const int* m, const double* const* alphas, const double* const* betas, int nc,
-                                                 const double* const* G, double* const* q, double* out_stats) {
-  HIPEIG_REQUIRE(A && B && m && alphas && betas && G && q, "null argument");
-  HIPEIG_REQUIRE(k == B->k, "the basis was kept for another number of columns");
-  HIPEIG_REQUIRE(nc == 1 || nc == 2 || nc == 4 || nc == 8, "1, 2, 4 or 8 combinations per column");
+extern "C" int hipeig_lanczos_combine(hipeig_ctx* c, hipeig_csr* A, const hipeig_lanczos_basis* B, int k,
+                                      const double* const* b, const int* m, const double* const* alphas,
+                                      const double* const* betas, int nc, const double* const* G, double* const* q,
+                                      double* out_stats) {
+  HIPEIG_REQUIRE(A && (B || b) && m && alphas && betas && G && q, "null argument");
   HIPEIG_REQUIRE(!c->collectives, "the Lanczos filter runs on whole vectors (no row partition)");
-  HIPEIG_REQUIRE(A->nrows == A->ncols && A->nrows == B->nrows, "the operator is not the one the basis was kept for");
+  if (B) {
+    HIPEIG_REQUIRE(k == B->k, "the basis was kept for another number of columns");
+    HIPEIG_REQUIRE(nc == 1 || nc == 2 || nc == 4 || nc == 8, "1, 2, 4 or 8 combinations per column");
+    HIPEIG_REQUIRE(A->nrows == A->ncols && A->nrows == B->nrows, "the operator is not the one the basis was kept for");
+  } else {
+    HIPEIG_REQUIRE(k >= 1 && k <= BCOO_KMAX, "1 to 8 right-hand sides per call");
+    HIPEIG_REQUIRE(nc == 1 || nc == 2, "one or two combinations per column");
+    HIPEIG_REQUIRE(A->nrows == A->ncols, "the Lanczos run needs a square operator");
+  }
+  for (int j = 0; j < k; ++j) {
+    HIPEIG_REQUIRE(m[j] >= 0, "negative number of terms");
+    HIPEIG_REQUIRE(!B || m[j] <= B->ran[j], "more terms than the steps the column ran");
+    HIPEIG_REQUIRE((B || b[j] != nullptr) && (m[j] == 0 || (alphas[j] && betas[j] && G[j])), "null column argument");
+    for (int cc = 0; cc < nc; ++cc)
+      HIPEIG_REQUIRE(q[j * nc + cc] != nullptr && (B || q[j * nc + cc] != b[j]), B ? "q must not be null" : "q must not be null or alias b");
+    HIPEIG_REQUIRE(m[j] == 0 || betas[j][0] > 0.0, B ? "a Lanczos vector past a breakdown was asked for" : "terms asked for a zero right-hand side");
+    for (int i = 1; i < m[j]; ++i) HIPEIG_REQUIRE(betas[j][i] > 0.0, "a Lanczos vector past a breakdown was asked for");
+  }
   if (out_stats) out_stats[0] = 0.0;
-  int p = 0, mmax = 0;
-  for (int j = 0; j < k; ++j) {
-    p = B->steps[j] > p ? B->steps[j] : p;
-    HIPEIG_REQUIRE(m[j] >= 0 && m[j] <= B->ran[j], "more terms than the steps the column ran");
-    mmax = m[j] > mmax ? m[j] : mmax;
-  }
-  if (mmax <= p) return hipeig_lanczos_basis_combine(c, B, k, m, betas, nc, G, q);
-  for (int j = 0; j < k; ++j) {
-    HIPEIG_REQUIRE(m[j] == 0 || (alphas[j] && betas[j] && G[j]), "null column argument");
-    for (int cc = 0; cc < nc; ++cc) HIPEIG_REQUIRE(q[j * nc + cc] != nullptr, "q must not be null");
-    for (int i = 0; i < m[j]; ++i) HIPEIG_REQUIRE(betas[j][i] > 0.0, "a Lanczos vector past a breakdown was asked for");
-  }
-#define LF_TAIL_CASE(KK, NN) \
-  if (B->K == KK && nc == NN) { \
-    const int rc = lf_combine_tail_impl<KK, NN>(c, A, B, k, m, alphas, betas, G, q, p, mmax); \
-    if (rc == 0 && out_stats) out_stats[0] = mmax - p; \
-    return rc; \
-  }
-  LF_TAIL_CASE(4, 1) LF_TAIL_CASE(4, 2) LF_TAIL_CASE(4, 4) LF_TAIL_CASE(4, 8)
-  LF_TAIL_CASE(8, 1) LF_TAIL_CASE(8, 2) LF_TAIL_CASE(8, 4) LF_TAIL_CASE(8, 8)
-#undef LF_TAIL_CASE
-  HIPEIG_REQUIRE(false, "unknown interleave width");
-}
-
-extern "C" int hipeig_lanczos_basis_combine(hipeig_ctx* c, const hipeig_lanczos_basis* B, int k, const int* m,
-                                            const double* const* betas, int nc, const double* const* G, double* const* q) {
-  HIPEIG_REQUIRE(B && m && betas && G && q, "null argument");
-  HIPEIG_REQUIRE(k == B->k, "the basis was kept for another number of columns");
-  HIPEIG_REQUIRE(nc == 1 || nc == 2 || nc == 4 || nc == 8, "1, 2, 4 or 8 combinations per column");
-  HIPEIG_REQUIRE(!c->collectives, "the Lanczos filter runs on whole vectors (no row partition)");
-  for (int j = 0; j < k; ++j) {
-    HIPEIG_REQUIRE(m[j] >= 0 && m[j] <= B->steps[j], "more terms than the vectors kept for the column");
-    HIPEIG_REQUIRE(m[j] == 0 || (betas[j] && G[j]), "null column argument");
-    for (int cc = 0; cc < nc; ++cc) HIPEIG_REQUIRE(q[j * nc + cc] != nullptr, "q must not be null");
-    for (int i = 0; i < m[j]; ++i) HIPEIG_REQUIRE(betas[j][i] > 0.0, "a Lanczos vector past a breakdown was asked for");
-  }
-  if (B->n == 0) return 0;
-#define LF_BC_CASE(KK, NN) if (B->K == KK && nc == NN) return lf_basis_combine_impl<KK, NN>(c, B, k, m, betas, G, q);
-  LF_BC_CASE(4, 1) LF_BC_CASE(4, 2) LF_BC_CASE(4, 4) LF_BC_CASE(4, 8)
-  LF_BC_CASE(8, 1) LF_BC_CASE(8, 2) LF_BC_CASE(8, 4) LF_BC_CASE(8, 8)
-#undef LF_BC_CASE
+  if (A->nrows == 0) return 0;
+  const int K = B ? B->K : lf_width(k);
+#define LF_PASS2_CASE(KK, NN) \
+  if (K == KK && nc == NN) return lf_pass2_impl<KK, NN>(c, A, B, k, b, m, alphas, betas, G, q, out_stats);
+  LF_PASS2_CASE(4, 1) LF_PASS2_CASE(4, 2) LF_PASS2_CASE(4, 4) LF_PASS2_CASE(4, 8)
+  LF_PASS2_CASE(8, 1) LF_PASS2_CASE(8, 2) LF_PASS2_CASE(8, 4) LF_PASS2_CASE(8, 8)
+#undef LF_PASS2_CASE
   HIPEIG_REQUIRE(false, "unknown interleave width");
 }
 

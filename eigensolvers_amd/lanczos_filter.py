@@ -8,14 +8,14 @@ the coefficients of shift k's iterate in that basis - numbers that follow from t
 * pass 1 (``lanczos_scalars_host`` / ``hipeig_lanczos_block_scalars``) runs the Lanczos recurrence and the per-shift
   rotation recurrences of ``shifted_minres_host`` and keeps scalars only: ``alpha_i``, ``beta_i`` and the stop steps;
 * the host turns them into ``g`` (``minres_coefficients``: the QR factors of the shifted tridiagonal, back substitution);
-* pass 2 (``lanczos_combine_host`` / ``hipeig_lanczos_block_combine``) repeats the recurrence from the stored scalars -
+* pass 2 (``lanczos_combine_host`` / ``hipeig_lanczos_combine``) repeats the recurrence from the stored scalars -
   no dot products - and accumulates ``q += g_i v_i``.
 
-With ``keepBasis`` / ``basis="keep"`` pass 1 keeps its vectors in device memory (``hipeig_lanczos_block_scalars_keep``) and
-pass 2 is one stream over them (``hipeig_lanczos_basis_combine``): no second set of products, any number of combinations.
-With ``keepPrefix`` / ``prefix=True`` on top, a basis that outgrows its byte budget keeps its first ``p`` vectors
-(``hipeig_lanczos_block_scalars_prefix``): the stream serves the terms ``i < p - 1`` and the recurrence restarts from the
-two last kept vectors (``hipeig_lanczos_basis_combine_tail``), ``m - p`` products instead of ``m - 1``.
+With ``keepBasis`` / ``basis="keep"`` pass 1 keeps its vectors in device memory (``basis_mode`` 1) and pass 2, handed that
+basis, is one stream over them: no second set of products, any number of combinations.  With ``keepPrefix`` /
+``prefix=True`` on top (``basis_mode`` 2), a basis that outgrows its byte budget keeps its first ``p`` vectors: the stream
+serves the terms ``i < p - 1`` and the recurrence restarts from the two last kept vectors, ``m - p`` products instead of
+``m - 1``.  ``prefix_split`` is the plan of all three.
 
 Both passes are an operator product plus a row epilogue, so up to 8 right-hand sides advance in lock step on the
 interleaved block products of ``csrc/spmm_device.h``.  The ``*_host`` functions are the NumPy statement - the
@@ -39,7 +39,7 @@ MAX_COLUMNS_PER_CALL = 8
 MAX_SHIFTS_PER_RUN = 32
 BASIS_MODES = ("recompute", "keep")
 BASIS_SAFETY = 0.9                       # share of the memory in sight a kept basis may take, as the contour pool's
-BASIS_COMBINE_WIDTHS = (8, 4, 2, 1)      # combinations per column one hipeig_lanczos_basis_combine call takes
+BASIS_COMBINE_WIDTHS = (8, 4, 2, 1)      # combinations per column one hipeig_lanczos_combine call takes from a basis
 
 
 def basis_budget(hbm_free, reusable, override=None, held=0):
@@ -407,51 +407,31 @@ class LanczosRun:
         dp = C.POINTER(C.c_double)
         for g, (lo, hi) in enumerate(self.groups):
             k = hi - lo
+            basis = self._bases[g] if g < len(self._bases) else None
             m = (C.c_int * k)(*[len(tabs[r]) for r in range(lo, hi)])
-            if g < len(self._bases) and self._bases[g] is not None:
-                al = [np.ascontiguousarray(self.scalars[r].alphas, dtype=np.float64) for r in range(lo, hi)]
-                be = [np.ascontiguousarray(self.scalars[r].betas, dtype=np.float64) for r in range(lo, hi)]
-                pa = (dp * k)(*[a.ctypes.data_as(dp) for a in al])
-                pb = (dp * k)(*[b.ctypes.data_as(dp) for b in be])
-                cols = [[None] * nc for _ in range(k)]
-                tail = prefix_split(max(m), self._basis_info(g)[0])[1]      # products per call: 0 from a whole basis
-                products, stats = 0, (C.c_double * 2)()
-                for c0, w in split_combinations(nc):
-                    part = [np.ascontiguousarray(tabs[r][:, c0:c0 + w]) for r in range(lo, hi)]
-                    pg = (dp * k)(*[t.ctypes.data_as(dp) for t in part])
-                    bufs = [ctx.alloc(n) for _ in range(k * w)]
-                    qt, keep2 = _ptr_table(bufs)
-                    if tail:
-                        _lib.call("hipeig_lanczos_basis_combine_tail", ctx.handle, self.H.handle, self._bases[g], k, m, pa, pb,
-                                  w, pg, qt, stats)
-                        if int(stats[0]) != tail:
-                            raise RuntimeError(f"the tail made {int(stats[0])} products, not {tail}")
-                        products += tail
-                    else:
-                        _lib.call("hipeig_lanczos_basis_combine", ctx.handle, self._bases[g], k, m, pb, w, pg, qt)
-                    for j in range(k):
-                        cols[j][c0:c0 + w] = [self.B[lo + j]._new(bufs[j * w + c]) for c in range(w)]
-                self.products_pass2.append(products)
-                for j in range(k):
-                    out.append(cols[j][0] if nc == 1 else HipComplexVector(*cols[j]) if nc == 2 else cols[j])
-                continue
             al = [np.ascontiguousarray(self.scalars[r].alphas, dtype=np.float64) for r in range(lo, hi)]
             be = [np.ascontiguousarray(self.scalars[r].betas, dtype=np.float64) for r in range(lo, hi)]
             pa = (dp * k)(*[a.ctypes.data_as(dp) for a in al])
             pb = (dp * k)(*[b.ctypes.data_as(dp) for b in be])
-            pg = (dp * k)(*[tabs[r].ctypes.data_as(dp) for r in range(lo, hi)])
             bt, keep1 = _ptr_table([b._buf for b in self.B[lo:hi]])
-            bufs = [ctx.alloc(n) for _ in range(k * nc)]
-            qt, keep2 = _ptr_table(bufs)
-            stats = (C.c_double * 2)()
-            _lib.call("hipeig_lanczos_block_combine", ctx.handle, self.H.handle, k, bt, m, pa, pb, nc, pg, qt, stats)
-            self.products_pass2.append(int(stats[0]))
+            # products per call: 0 from a whole basis, all but the last term's without one
+            expect = prefix_split(max(m), self._basis_info(g)[0])[1] if basis is not None else max(max(m) - 1, 0)
+            cols = [[None] * nc for _ in range(k)]
+            products, stats = 0, (C.c_double * 2)()
+            for c0, w in split_combinations(nc):
+                part = [np.ascontiguousarray(tabs[r][:, c0:c0 + w]) for r in range(lo, hi)]
+                pg = (dp * k)(*[t.ctypes.data_as(dp) for t in part])
+                bufs = [ctx.alloc(n) for _ in range(k * w)]
+                qt, keep2 = _ptr_table(bufs)
+                _lib.call("hipeig_lanczos_combine", ctx.handle, self.H.handle, basis, k, bt, m, pa, pb, w, pg, qt, stats)
+                if int(stats[0]) != expect:
+                    raise RuntimeError(f"pass 2 made {int(stats[0])} products, not {expect}")
+                products += expect
+                for j in range(k):
+                    cols[j][c0:c0 + w] = [self.B[lo + j]._new(bufs[j * w + c]) for c in range(w)]
+            self.products_pass2.append(products)
             for j in range(k):
-                b = self.B[lo + j]
-                if nc == 1:
-                    out.append(b._new(bufs[j]))
-                else:
-                    out.append(HipComplexVector(b._new(bufs[2 * j]), b._new(bufs[2 * j + 1])))
+                out.append(cols[j][0] if nc == 1 else HipComplexVector(*cols[j]) if nc == 2 else cols[j])
         return out
 
 
@@ -487,12 +467,12 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None,
     grouped into calls of 8, each in lock step on block products.  Tolerances and the step limit come from
     ``B[0].options["linearSystemArgs"]`` as in ``solve_shifts``.  Nothing is raised here: ``run.info`` tells.
 
-    ``keepBasis``: every group keeps its Lanczos vectors in device memory (``hipeig_lanczos_block_scalars_keep``, the same
+    ``keepBasis``: every group keeps its Lanczos vectors in device memory (``basis_mode`` 1, the same
     scalars) as long as the byte budget allows - ``basisBytes`` for the whole run, by default ``basis_budget`` of the free
     device memory.  A group whose basis does not fit finishes as a plain pass 1; ``run.basis_kept`` tells.
 
-    ``keepPrefix`` (with ``keepBasis``): such a group keeps the vectors that fit instead
-    (``hipeig_lanczos_block_scalars_prefix``, again the same scalars); ``run.basis_vectors`` tells how many."""
+    ``keepPrefix`` (with ``keepBasis``): such a group keeps the vectors that fit instead (``basis_mode`` 2, again the same
+    scalars); ``run.basis_vectors`` tells how many."""
     from . import _lib
     from .hip_vector import _ptr_table
     keepPrefix = _checked_prefix(keepPrefix, keepBasis, "lanczos_run(keepPrefix=True)")
@@ -522,16 +502,12 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None,
         info = (C.c_int * k)()
         stats = (C.c_double * (1 + k))()
         dp = C.POINTER(C.c_double)
-        if keepBasis:
-            basis = C.c_void_p()
-            budget = _default_basis_budget(ctx, basisBytes, run.basis_bytes)
-            _lib.call("hipeig_lanczos_block_scalars_prefix" if keepPrefix else "hipeig_lanczos_block_scalars_keep", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
-                      alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats, budget, C.byref(basis))
-            run._bases.append(C.c_void_p(basis.value) if basis.value else None)
-        else:
-            _lib.call("hipeig_lanczos_block_scalars", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
-                      alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats)
-            run._bases.append(None)
+        basis = C.c_void_p()
+        budget = _default_basis_budget(ctx, basisBytes, run.basis_bytes) if keepBasis else 0
+        _lib.call("hipeig_lanczos_block_scalars", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
+                  alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats,
+                  2 if keepPrefix else 1 if keepBasis else 0, budget, C.byref(basis))
+        run._bases.append(C.c_void_p(basis.value) if basis.value else None)
         run.groups.append((lo, hi))
         run.products_pass1.append(int(stats[0]))
         for j in range(k):

@@ -335,57 +335,43 @@ int hipeig_minres_shifts(hipeig_ctx* ctx, hipeig_csr* A, double sign, int nshift
  * shifts of sign*(z I - H) - scalars only.  alphas: k rows of maxiter doubles, betas: k rows of maxiter + 1 (betas[0] =
  * ||b||; step i, 0-based, yields alphas[i] and betas[i + 1]); iterations / estimates: k rows of nshift (stop step, |tau|);
  * info[j] = 0, or maxiter when a shift of column j was still live there.  out_stats (may be NULL): 1 + k doubles - block
- * products of the run, then the steps each column ran.  One GPU, whole vectors: a context with collectives is refused.  */
+ * products of the run, then the steps each column ran.  One GPU, whole vectors: a context with collectives is refused.
+ *
+ * basis_mode 0: the vectors live in a ring of three; basis_bytes is not read and basis may be NULL.
+ * basis_mode 1 (lanczos_filter.py, lanczos_run(keepBasis=True)): the vectors are KEPT in device memory - step k's new
+ * vector goes to slot k + 1 of a basis carved from segments allocated while the run advances (HIPEIG_LF_SEGMENT slots each,
+ * default 32) instead of over the oldest ring buffer: the same kernels on the same operands, so every result equals mode
+ * 0's (bit for bit with the row-owner sweep).  basis_bytes: byte budget of the segments.  When the next segment would
+ * exceed it, or the device has no room, the run goes on in the ring and *basis is NULL (not an error); otherwise *basis
+ * owns the vectors until hipeig_lanczos_basis_release.
+ * basis_mode 2 (keepPrefix=True): as mode 1 while segments can be had.  When the next segment is refused the segments held
+ * stay and are written to their last slot - p = segments * slots vectors - and from step p - 1 on the new vector goes to
+ * the ring; steps p - 1 and p read their operands from the slots, so kernels, operands and scalars are still mode 0's.
+ * The basis then holds min(steps of column j, p) vectors per column.  A run that stops before p ends as a whole basis;
+ * *basis is NULL only when not even the first segment fits.  The workspace of the pass 2 that follows (nc <= 2) is reserved
+ * before the first segment.                                                                                            */
+typedef struct hipeig_lanczos_basis hipeig_lanczos_basis;
 int hipeig_lanczos_block_scalars(hipeig_ctx* ctx, hipeig_csr* A, double sign, int k, const double* const* b,
                                  int nshift, const double* zr, const double* zi, double rtol, double atol,
                                  int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
-                                 int* info, double* out_stats);
-/* PASS 2 of the same (feast.py:189-200): the Lanczos vectors of the k columns rebuilt from pass 1's scalars (alphas[j],
- * betas[j]: host arrays of m[j] and m[j] + 1 doubles) - no dot products - and q[j*nc + c] = sum_{i < m[j]} G[j][i*nc + c] v_i
- * for c < nc (1 or 2) accumulated in the block product's epilogue; q: k*nc vectors of n doubles, overwritten.  Column j stops
- * after its own m[j] terms; the last term needs no product: out_stats[0] (may be NULL) = max_j m[j] - 1 block products. */
-int hipeig_lanczos_block_combine(hipeig_ctx* ctx, hipeig_csr* A, int k, const double* const* b, const int* m,
-                                 const double* const* alphas, const double* const* betas, int nc,
-                                 const double* const* G, double* const* q, double* out_stats);
-
-/* The same pass 1 with its Lanczos vectors KEPT in device memory (lanczos_filter.py, lanczos_run(keepBasis=True)): step k's
- * new vector goes to slot k + 1 of a basis carved from segments allocated while the run advances (HIPEIG_LF_SEGMENT slots
- * each, default 32) instead of over the oldest of three ring buffers - the same kernels on the same operands, so every
- * result equals hipeig_lanczos_block_scalars' (bit for bit with the row-owner sweep).  basis_bytes: byte budget of the
- * segments.  When the next segment would exceed it, or the device has no room, the run goes on in the ring and *basis is
- * NULL (not an error); otherwise *basis owns the vectors until hipeig_lanczos_basis_release.                          */
-typedef struct hipeig_lanczos_basis hipeig_lanczos_basis;
-int hipeig_lanczos_block_scalars_keep(hipeig_ctx* ctx, hipeig_csr* A, double sign, int k, const double* const* b,
-                                      int nshift, const double* zr, const double* zi, double rtol, double atol,
-                                      int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
-                                      int* info, double* out_stats, int64_t basis_bytes, hipeig_lanczos_basis** basis);
-/* PASS 2 from a kept basis (lanczos_filter.py, LanczosRun.combine): q[j*nc + c] = sum_{i < m[j]} G[j][i*nc + c] v_i for
- * c < nc (1, 2, 4 or 8), v_i = r_i / betas[j][i], in one stream over the stored vectors - no operator product, any number
- * of calls per basis.  k must be the basis's column count, m[j] at most the vectors kept for column j; betas[j]: host
- * array of at least m[j] doubles (pass 1's).  With the row-owner sweep the result equals hipeig_lanczos_block_combine's
- * bit for bit.                                                                                                        */
-int hipeig_lanczos_basis_combine(hipeig_ctx* ctx, const hipeig_lanczos_basis* basis, int k, const int* m,
-                                 const double* const* betas, int nc, const double* const* G, double* const* q);
-/* Keep mode that holds on to a PREFIX (lanczos_filter.py, lanczos_run(keepBasis=True, keepPrefix=True)): the arguments and,
- * while segments can be had, the behaviour of hipeig_lanczos_block_scalars_keep.  When the next segment is refused (budget
- * or device memory) the segments held stay and are written to their last slot - p = segments * slots vectors - and from
- * step p - 1 on the new vector goes to the ring of three; steps p - 1 and p read their operands from the slots, so the
- * kernels, operands and scalars are the plain run's (bit for bit with the row-owner sweep).  The basis then holds
- * min(steps of column j, p) vectors per column.  A run that stops before p ends as a whole basis; *basis is NULL only when
- * not even the first segment fits.  The workspace of the tail pass (nc <= 2) is reserved before the first segment.      */
-int hipeig_lanczos_block_scalars_prefix(hipeig_ctx* ctx, hipeig_csr* A, double sign, int k, const double* const* b,
-                                        int nshift, const double* zr, const double* zi, double rtol, double atol,
-                                        int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
-                                        int* info, double* out_stats, int64_t basis_bytes, hipeig_lanczos_basis** basis);
-/* PASS 2 from a prefix (lanczos_filter.py, LanczosRun.combine): the sums of hipeig_lanczos_block_combine for nc = 1, 2, 4
- * or 8 from a basis that holds p vectors.  With mmax = max_j m[j] <= p it is hipeig_lanczos_basis_combine.  Otherwise the
- * stream takes the terms i < p - 1, r_{p-2} and r_{p-1} are copied out of their slots (the basis is never written) and
- * the recurrence of pass 2 runs from step p - 1: out_stats[0] (may be NULL) = mmax - p block products instead of mmax - 1.
- * m[j] at most the steps column j ran; alphas[j], betas[j]: pass 1's.  Every element meets the operations of the product
- * pass in its order: with the row-owner sweep the result equals it bit for bit.                                        */
-int hipeig_lanczos_basis_combine_tail(hipeig_ctx* ctx, hipeig_csr* A, const hipeig_lanczos_basis* basis, int k,
-                                      const int* m, const double* const* alphas, const double* const* betas, int nc,
-                                      const double* const* G, double* const* q, double* out_stats);
+                                 int* info, double* out_stats, int basis_mode, int64_t basis_bytes,
+                                 hipeig_lanczos_basis** basis);
+/* PASS 2 of the same (lanczos_filter.py, LanczosRun.combine): q[j*nc + c] = sum_{i < m[j]} G[j][i*nc + c] v_i for c < nc, with
+ * pass 1's scalars (alphas[j], betas[j]: host arrays of at least m[j] and m[j] + 1 doubles); q: k*nc vectors of n doubles,
+ * overwritten.  Column j stops after its own m[j] terms, at most the steps it ran.  With mmax = max_j m[j]:
+ *   basis NULL: the Lanczos vectors are rebuilt from b (k columns, read only here; q must not alias them) by the
+ *     recurrence - no dot products - and the sums accumulated in the block product's epilogue, nc = 1 or 2; the last term
+ *     needs no product: mmax - 1 block products;
+ *   a basis that holds p >= mmax vectors: one stream over the stored vectors v_i = r_i / betas[j][i], nc = 1, 2, 4 or 8,
+ *     no product, any number of calls per basis; k must be the basis's column count and A the operator it was kept for;
+ *   a basis that holds p < mmax: the stream takes the terms i < p - 1, r_{p-2} and r_{p-1} are copied out of their slots
+ *     (the basis is never written) and the recurrence runs from step p - 1: mmax - p block products.
+ * out_stats[0] (may be NULL) = block products made.  Every element meets the same operations in the same order in the
+ * three situations: with the row-owner sweep the results are equal bit for bit.                                        */
+int hipeig_lanczos_combine(hipeig_ctx* ctx, hipeig_csr* A, const hipeig_lanczos_basis* basis, int k,
+                           const double* const* b, const int* m, const double* const* alphas,
+                           const double* const* betas, int nc, const double* const* G, double* const* q,
+                           double* out_stats);
 /* What a kept basis holds (lanczos_filter.py, LanczosRun.basis_bytes and default_basis_budget): info[0] vectors kept (the
  * largest column's; behind a prefix at most its p), [1] bytes of its segments, [2] interleave width K, [3] rows, [4] columns, [5] bytes of released
  * segments the context would hand out again, [6] segments, [7] slots per segment.  basis may be NULL: only [5] is set. */

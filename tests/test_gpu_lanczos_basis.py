@@ -1,184 +1,35 @@
-"""The kept Lanczos basis on the device (``csrc/lanczos_filter.hip``: ``hipeig_lanczos_block_scalars_keep``,
-``hipeig_lanczos_basis_combine`` behind ``lanczos_run(keepBasis=True)``, ``lanczos_filter(basis="keep")`` and the
-``HipVector`` option ``"lanczosBasis"``) against the two-pass path it replaces.
+"""The kept Lanczos basis on the device (``csrc/lanczos_filter.hip``: ``hipeig_lanczos_block_scalars`` with ``basis_mode`` 1
+and ``hipeig_lanczos_combine`` on its basis, behind ``lanczos_run(keepBasis=True)``, ``lanczos_filter(basis="keep")`` and
+the ``HipVector`` option ``"lanczosBasis"``) against the two-pass path it replaces.
 
 Every case fails without the feature: the names do not exist.
 
 With the row-owner sweep (block variant 1) the kept path runs pass 1's kernels on pass 1's operands and the combination
 puts every element through the product pass's operations in its order, so scalars and vectors are compared with
 ``array_equal``.  With the window-blocked sweep (variant 2, LDS atomics, add order not fixed) the checks are those of
-``test_gpu_lanczos_filter.py``, restated here: stop steps within ``STEP_DIFFERENCE_BOUND`` of the shifted-MINRES twin
+``test_gpu_lanczos_filter.py`` (helpers and bounds: ``_lanczos_cases.py``): stop steps within ``STEP_DIFFERENCE_BOUND`` of the shifted-MINRES twin
 (max(3, 2 * largest difference observed), EXPERIMENTS.md R9), the filtered vectors within the bound derived there from
 the residual targets - ``||q - q_exact|| <= sum_j |c_j| (1.01 target + 100 eps (|z_j| + ||H||_inf) ||x_j||) /
 dist(z_j, spectrum)`` against the ``eigh`` filter - and single solutions within its true-residual bound."""
-import importlib
-import math
 import warnings
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from eigensolvers_amd import feast as pf
-from eigensolvers_amd.generators import gapped_csr_host
-from eigensolvers_amd.shifted_minres import shifted_minres_host
-
-lf = importlib.import_module("eigensolvers_amd.lanczos_filter")       # the package exports the function of the same name
+from _lanczos_cases import (EPS, FAR, HI, LO, NEAR, W8, Z8, arrays, block_variant, build_problems, check_filter, check_steps,
+                            device_columns, lf, options, residual_bound, reusable_bytes, same_scalars,
+                            single_solution_tables, slot_bytes, spectrum, twin)
 
 pytestmark = pytest.mark.gpu
 
-EPS = np.finfo(float).eps
-LO, HI = (1e-5, 1e-7), (1e-10, 1e-12)
-STEP_DIFFERENCE_BOUND = 3          # max(3, 2 * largest difference observed), see the module docstring
 NCOLS = 16
-
-
-def contour(nc):
-    """(shifts, FEAST's weights -0.5 w r phase) of the nc-node Legendre half contour of [-0.21, 0.21]."""
-    gk, wk = pf.quadraturePointsWeights(nc, "legendre", positiveHalf=True)
-    zs, ws = [], []
-    for g, w in zip(gk, wk):
-        theta, z = pf.contour_point(-0.21, 0.21, g)
-        zs.append(z)
-        ws.append(-0.5 * w * 0.21 * (math.cos(theta) + 1j * math.sin(theta)))
-    return zs, ws
-
-
-Z8, W8 = contour(16)
-NEAR, FAR = int(np.argmin([abs(z.imag) for z in Z8])), int(np.argmax([abs(z.imag) for z in Z8]))
-
-
-def odd_operator():
-    """n = 1037 (no tile, wave or vector width divides it): a random sparse symmetric matrix plus a diagonal of the
-    generator's kind - +-(1..3) except 8 rows inside the contour's window."""
-    n = 1037
-    rng = np.random.default_rng(5)
-    R = sp.random(n, n, density=0.01, random_state=rng, format="csr")
-    d = rng.choice([-1.0, 1.0], n) * rng.uniform(1.0, 3.0, n)
-    d[::130] = np.linspace(-0.2, 0.2, len(d[::130]))
-    return (0.05 * (R + R.T) + sp.diags(d)).tocsr()
-
-
-def tridiagonal100():
-    """One workgroup: diagonal +-(1..1.5), off-diagonal 0.1, no eigenvalue in (-0.8, 0.8)."""
-    n = 100
-    d = np.concatenate([np.linspace(-1.5, -1.0, n // 2), np.linspace(1.0, 1.5, n - n // 2)])
-    return sp.diags([np.full(n - 1, 0.1), d, np.full(n - 1, 0.1)], [-1, 0, 1]).tocsr()
-
-
-def host_operator(name):
-    if name == "tri100":
-        return tridiagonal100()
-    if name == "gapped4000":
-        return gapped_csr_host(4000, 32, seed=7)
-    return odd_operator()
 
 
 @pytest.fixture(scope="module")
 def problems(hip):
     """name -> (host CSR, device operator, host right-hand sides [NCOLS, n]), built once."""
-    out = {}
-    for name in ("tri100", "gapped4000", "odd1037"):
-        Hh = host_operator(name)
-        Hd = hip.HipCsrOperator.generate(4000, 32, seed=7) if name == "gapped4000" else hip.HipCsrOperator.from_scipy(Hh)
-        B = np.random.default_rng(9).standard_normal((NCOLS, Hh.shape[0]))
-        out[name] = (Hh, Hd, B / np.linalg.norm(B, axis=1)[:, None])
-    return out
-
-
-_spectra = {}
-
-
-def spectrum(name, Hh):
-    if name not in _spectra:
-        _spectra[name] = np.linalg.eigh(Hh.toarray())
-    return _spectra[name]
-
-
-_twin_cache = {}
-
-
-def twin(key, Hh, b, shifts, rtol, atol, sign, maxiter=4000):
-    """(steps, estimates, converged, ||x_j||) of the shifted-MINRES twin for one column, computed once per key."""
-    key = (key, tuple(shifts), rtol, atol, sign, maxiter)
-    if key not in _twin_cache:
-        x, its, est, conv = shifted_minres_host(lambda v: Hh @ v, b, shifts, rtol, atol, maxiter, sign)
-        _twin_cache[key] = (its, est, conv, np.linalg.norm(x, axis=1))
-    return _twin_cache[key]
-
-
-def options(rtol, atol, maxiter=4000):
-    return {"linearSystemArgs": {"linearSolver": "lanczos_filter", "linearIter": maxiter, "linear_tol": rtol, "linear_atol": atol}}
-
-
-def device_columns(hip, B, rtol, atol, maxiter=4000):
-    o = options(rtol, atol, maxiter)
-    return [hip.HipVector(np.array(b, dtype=float), o) for b in B]
-
-
-def exact_filter(lam, U, b, zs, ws, sign):
-    f = sum((w * sign / (z - lam)).real for z, w in zip(zs, ws))
-    return U @ (f * (U.T @ b))
-
-
-def filter_bound(Hh, lam, zs, ws, xnorms, target):
-    hinf = abs(Hh).sum(axis=1).max()
-    return sum(abs(w) * (1.01 * target + 100 * EPS * (abs(z) + hinf) * xn) / np.min(np.abs(z - lam))
-               for z, w, xn in zip(zs, ws, xnorms))
-
-
-def residual_bound(Hh, z, x, target):
-    hinf = abs(Hh).sum(axis=1).max()
-    return 1.01 * target + 100 * EPS * (abs(z) + hinf) * np.linalg.norm(x)
-
-
-def check_steps(label, device_its, twin_its):
-    diff = [int(d) - int(t) for d, t in zip(device_its, twin_its)]
-    print(f"STEPS {label} twin={list(map(int, twin_its))} device-twin={diff}")
-    assert max(abs(d) for d in diff) <= STEP_DIFFERENCE_BOUND, (label, diff, list(twin_its))
-    assert all(d <= math.ceil(1.1 * t) for d, t in zip(device_its, twin_its)), (label, diff)
-
-
-def check_filter(label, name, Hh, b, q, zs, ws, xnorms, target, sign):
-    lam, U = spectrum(name, Hh)
-    err = np.linalg.norm(q - exact_filter(lam, U, b, zs, ws, sign))
-    bound = filter_bound(Hh, lam, zs, ws, xnorms, target)
-    print(f"FILTER {label} error {err:.3e} bound {bound:.3e} used {err / bound:.3f}")
-    assert np.isfinite(q).all() and err <= bound, (label, err, bound)
-
-
-def same_scalars(a, b):
-    return len(a) == len(b) and all(np.array_equal(x, y) for sa, sb in zip(a, b) for x, y in zip(sa, sb))
-
-
-def single_solution_tables(run, j, sign):
-    """NC = 2 tables (Re y, Im y) of shift j's MINRES iterate, per column."""
-    G = []
-    for sc in run.scalars:
-        y = lf.minres_coefficients(sc.alphas, sc.betas, Z8[j], sc.iterations[j], sign)
-        G.append(np.stack([y.real, y.imag], axis=1))
-    return G
-
-
-def arrays(vs):
-    return [v.array for v in vs]
-
-
-class block_variant:
-    def __init__(self, Hd, variant):
-        self.Hd, self.variant = Hd, variant
-
-    def __enter__(self):
-        self.Hd.set_block_variant(self.variant)
-
-    def __exit__(self, *exc):
-        self.Hd.set_block_variant(0)
-
-
-def slot_bytes(n, k):
-    """Bytes of one slot of a k-column group: the interleaved block, padded to 32 doubles."""
-    K = 4 if k <= 4 else 8
-    return ((n * K + 31) // 32 * 32) * 8
+    return build_problems(hip, ("tri100", "gapped4000", "odd1037"), NCOLS)
 
 
 # ---- 1. pass 1 is unchanged ------------------------------------------------------------------------------------------
@@ -472,22 +323,14 @@ def test_a_budget_for_one_group_of_two(hip, problems):
 def test_released_segments_are_handed_out_again(hip, problems):
     name, K = "odd1037", 3
     Hh, Hd, B = problems[name]
-    import ctypes as C
-    from eigensolvers_amd import _lib
-
-    def reusable(ctx):
-        info = (C.c_int64 * 8)()
-        _lib.call("hipeig_lanczos_basis_info", ctx.handle, None, info)
-        return info[5]
-
     cols = device_columns(hip, B[:K], *LO)
     ctx = cols[0].ctx
     run = hip.lanczos_run(Hd, cols, Z8, keepBasis=True)
-    held, before = run.basis_bytes, reusable(ctx)
+    held, before = run.basis_bytes, reusable_bytes(ctx)
     run.release()
-    assert held > 0 and reusable(ctx) == before + held
+    assert held > 0 and reusable_bytes(ctx) == before + held
     again = hip.lanczos_run(Hd, cols, Z8, keepBasis=True)
-    assert again.basis_bytes == held and reusable(ctx) <= before
+    assert again.basis_bytes == held and reusable_bytes(ctx) <= before
     again.release()
 
 

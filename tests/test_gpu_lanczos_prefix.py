@@ -1,5 +1,5 @@
-"""A Lanczos basis kept as a prefix on the device (``csrc/lanczos_filter.hip``: ``hipeig_lanczos_block_scalars_prefix``,
-``hipeig_lanczos_basis_combine_tail`` behind ``lanczos_run(keepBasis=True, keepPrefix=True)``,
+"""A Lanczos basis kept as a prefix on the device (``csrc/lanczos_filter.hip``: ``hipeig_lanczos_block_scalars`` with
+``basis_mode`` 2 and ``hipeig_lanczos_combine`` on its basis, behind ``lanczos_run(keepBasis=True, keepPrefix=True)``,
 ``lanczos_filter(basis="keep", prefix=True)`` and the ``HipVector`` option ``"lanczosBasisPrefix"``) against the plain
 two-pass path.
 
@@ -9,129 +9,27 @@ With the row-owner sweep (block variant 1) pass 1 runs the plain run's kernels o
 a slot or in the ring, and pass 2 puts every element through the product pass's operations in ascending order - the
 stream for the terms ``i < p - 1``, the product loop from step ``p - 1`` - so scalars and vectors are compared with
 ``array_equal``.  With the window-blocked sweep (variant 2, LDS atomics, add order not fixed) the checks are those of
-``test_gpu_lanczos_basis.py``, restated here: stop steps within ``STEP_DIFFERENCE_BOUND`` of the shifted-MINRES twin and
+``test_gpu_lanczos_basis.py`` (helpers and bounds: ``_lanczos_cases.py``): stop steps within ``STEP_DIFFERENCE_BOUND`` of the shifted-MINRES twin and
 the filtered vectors within ``||q - q_exact|| <= sum_j |c_j| (1.01 target + 100 eps (|z_j| + ||H||_inf) ||x_j||) /
 dist(z_j, spectrum)`` against the ``eigh`` filter.  No tolerance is new."""
-import ctypes as C
-import importlib
-import math
 import warnings
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
-from eigensolvers_amd import feast as pf
-from eigensolvers_amd.generators import gapped_csr_host
-from eigensolvers_amd.shifted_minres import shifted_minres_host
-
-lf = importlib.import_module("eigensolvers_amd.lanczos_filter")       # the package exports the function of the same name
+from _lanczos_cases import (FAR, LO, NEAR, STEP_DIFFERENCE_BOUND, W8, Z8, all_equal, arrays, block_variant, build_problems,
+                            device_columns, filter_bound, lf, options, reusable_bytes, same_scalars, single_solution_tables,
+                            slot_bytes, spectrum, twin)
 
 pytestmark = pytest.mark.gpu
 
-EPS = np.finfo(float).eps
-LO = (1e-5, 1e-7)
-STEP_DIFFERENCE_BOUND = 3          # max(3, 2 * largest difference observed), EXPERIMENTS.md R9
 NCOLS = 16
-
-
-def contour(nc):
-    """(shifts, FEAST's weights -0.5 w r phase) of the nc-node Legendre half contour of [-0.21, 0.21]."""
-    gk, wk = pf.quadraturePointsWeights(nc, "legendre", positiveHalf=True)
-    zs, ws = [], []
-    for g, w in zip(gk, wk):
-        theta, z = pf.contour_point(-0.21, 0.21, g)
-        zs.append(z)
-        ws.append(-0.5 * w * 0.21 * (math.cos(theta) + 1j * math.sin(theta)))
-    return zs, ws
-
-
-Z8, W8 = contour(16)
-NEAR, FAR = int(np.argmin([abs(z.imag) for z in Z8])), int(np.argmax([abs(z.imag) for z in Z8]))
-
-
-def odd_operator():
-    """n = 1037 (no tile, wave or vector width divides it): a random sparse symmetric matrix plus a diagonal +-(1..3)
-    except 8 rows inside the contour's window."""
-    n = 1037
-    rng = np.random.default_rng(5)
-    R = sp.random(n, n, density=0.01, random_state=rng, format="csr")
-    d = rng.choice([-1.0, 1.0], n) * rng.uniform(1.0, 3.0, n)
-    d[::130] = np.linspace(-0.2, 0.2, len(d[::130]))
-    return (0.05 * (R + R.T) + sp.diags(d)).tocsr()
-
-
-def tridiagonal100():
-    """One workgroup: diagonal +-(1..1.5), off-diagonal 0.1, no eigenvalue in (-0.8, 0.8)."""
-    n = 100
-    d = np.concatenate([np.linspace(-1.5, -1.0, n // 2), np.linspace(1.0, 1.5, n - n // 2)])
-    return sp.diags([np.full(n - 1, 0.1), d, np.full(n - 1, 0.1)], [-1, 0, 1]).tocsr()
 
 
 @pytest.fixture(scope="module")
 def problems(hip):
     """name -> (host CSR, device operator, host right-hand sides [NCOLS, n]), built once."""
-    out = {}
-    for name in ("tri100", "gapped4000", "odd1037"):
-        Hh = tridiagonal100() if name == "tri100" else gapped_csr_host(4000, 32, seed=7) if name == "gapped4000" else odd_operator()
-        Hd = hip.HipCsrOperator.generate(4000, 32, seed=7) if name == "gapped4000" else hip.HipCsrOperator.from_scipy(Hh)
-        B = np.random.default_rng(9).standard_normal((NCOLS, Hh.shape[0]))
-        out[name] = (Hh, Hd, B / np.linalg.norm(B, axis=1)[:, None])
-    return out
-
-
-def options(rtol, atol, maxiter=4000):
-    return {"linearSystemArgs": {"linearSolver": "lanczos_filter", "linearIter": maxiter, "linear_tol": rtol, "linear_atol": atol}}
-
-
-def device_columns(hip, B, rtol=LO[0], atol=LO[1]):
-    o = options(rtol, atol)
-    return [hip.HipVector(np.array(b, dtype=float), o) for b in B]
-
-
-def same_scalars(a, b):
-    return len(a) == len(b) and all(np.array_equal(x, y) for sa, sb in zip(a, b) for x, y in zip(sa, sb))
-
-
-def single_solution_tables(run, j, sign=1.0):
-    """NC = 2 tables (Re y, Im y) of shift j's MINRES iterate, per column."""
-    G = []
-    for sc in run.scalars:
-        y = lf.minres_coefficients(sc.alphas, sc.betas, Z8[j], sc.iterations[j], sign)
-        G.append(np.stack([y.real, y.imag], axis=1))
-    return G
-
-
-def arrays(vs):
-    return [v.array for v in vs]
-
-
-def all_equal(xs, ys):
-    return len(xs) == len(ys) and all(np.array_equal(x, y) for x, y in zip(xs, ys))
-
-
-class block_variant:
-    def __init__(self, Hd, variant):
-        self.Hd, self.variant = Hd, variant
-
-    def __enter__(self):
-        self.Hd.set_block_variant(self.variant)
-
-    def __exit__(self, *exc):
-        self.Hd.set_block_variant(0)
-
-
-def slot_bytes(n, k):
-    """Bytes of one slot of a k-column group: the interleaved block, padded to 32 doubles."""
-    K = 4 if k <= 4 else 8
-    return ((n * K + 31) // 32 * 32) * 8
-
-
-def reusable_bytes(ctx):
-    from eigensolvers_amd import _lib
-    info = (C.c_int64 * 8)()
-    _lib.call("hipeig_lanczos_basis_info", ctx.handle, None, info)
-    return info[5]
+    return build_problems(hip, ("tri100", "gapped4000", "odd1037"), NCOLS)
 
 
 def segments(monkeypatch, seg, chunk=None):
@@ -148,7 +46,7 @@ def odd5(hip, problems):
     product pass makes of them - the reference of the cases below, computed once."""
     Hh, Hd, B = problems["odd1037"]
     with block_variant(Hd, 1):
-        cols = device_columns(hip, B[:5])
+        cols = device_columns(hip, B[:5], *LO)
         plain = hip.lanczos_run(Hd, cols, Z8)
         assert plain.converged and min(len(s.alphas) for s in plain.scalars) > 50
         tables = {"filter": lf.filter_coefficients(plain.scalars, Z8, W8), "near": single_solution_tables(plain, NEAR),
@@ -190,6 +88,26 @@ def test_hand_over_and_combination(hip, problems, odd5, monkeypatch, seg, chunk,
             assert all_equal(got, combined[key])
 
 
+@pytest.mark.parametrize("p", [1, 2, 3])
+def test_the_shortest_prefixes(hip, problems, odd5, monkeypatch, p):
+    """Segments of one slot and room for p of them: where pass 2's plan without a basis and its plan behind a prefix
+    meet - p = 1: no stream term, the recurrence starts at step 0 with r_0 from slot 0 and zeros for r_{-1}; p = 2: still
+    no stream term, first product step 1; p = 3: one stream term."""
+    Hh, Hd, B = problems["odd1037"]
+    cols, plain, tables, combined = odd5
+    segments(monkeypatch, 1)
+    with block_variant(Hd, 1):
+        run = hip.lanczos_run(Hd, cols, Z8, keepBasis=True, keepPrefix=True, basisBytes=p * slot_bytes(1037, 5) + 100)
+        assert same_scalars(plain.scalars, run.scalars)
+        assert run.basis_vectors == [p]
+        for key in ("filter", "near"):
+            G = tables[key]
+            got = arrays(run.combine(G))
+            assert run.products_pass2 == [max(len(g) for g in G) - p]
+            assert all_equal(got, combined[key]), (key, p)
+        run.release()
+
+
 # ---- 3. masks around the seam ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key", ["filter", "near"])
 def test_masks_around_the_seam(hip, problems, odd5, monkeypatch, key):
@@ -228,7 +146,7 @@ def test_wide_tables_from_a_prefix(hip, problems, monkeypatch):
     monkeypatch.delenv("HIPEIG_LF_CHUNK", raising=False)
     rng = np.random.default_rng(21)
     with block_variant(Hd, 1):
-        cols = device_columns(hip, B[:K])
+        cols = device_columns(hip, B[:K], *LO)
         plain = hip.lanczos_run(Hd, cols, Z8)
         run = hip.lanczos_run(Hd, cols, Z8, keepBasis=True, keepPrefix=True, basisBytes=3 * 32 * slot_bytes(4000, K) + 8)
         assert same_scalars(plain.scalars, run.scalars)
@@ -280,24 +198,6 @@ def test_enough_budget_and_too_little(hip, problems, odd5, monkeypatch):
 
 
 # ---- 6. the window-blocked sweep ---------------------------------------------------------------------------------------
-_spectra, _twins = {}, {}
-
-
-def twin(name, r, Hh, b, rtol, atol):
-    """(steps, ||x_j||) of the shifted-MINRES twin for one column, computed once."""
-    if (name, r) not in _twins:
-        x, its, est, conv = shifted_minres_host(lambda v: Hh @ v, b, Z8, rtol, atol, 4000, 1.0)
-        assert conv.all()
-        _twins[name, r] = (its, np.linalg.norm(x, axis=1))
-    return _twins[name, r]
-
-
-def filter_bound(Hh, lam, zs, ws, xnorms, target):
-    hinf = abs(Hh).sum(axis=1).max()
-    return sum(abs(w) * (1.01 * target + 100 * EPS * (abs(z) + hinf) * xn) / np.min(np.abs(z - lam))
-               for z, w, xn in zip(zs, ws, xnorms))
-
-
 @pytest.mark.parametrize("name,K,seg,nseg", [("odd1037", 5, 5, 4), ("tri100", 8, 3, 3)])
 def test_prefix_with_the_window_blocked_sweep(hip, problems, monkeypatch, name, K, seg, nseg):
     Hh, Hd, B = problems[name]
@@ -305,17 +205,16 @@ def test_prefix_with_the_window_blocked_sweep(hip, problems, monkeypatch, name, 
     n, p = Hh.shape[0], seg * nseg
     segments(monkeypatch, seg)
     with block_variant(Hd, 2):
-        run = hip.lanczos_run(Hd, device_columns(hip, B[:K]), Z8, keepBasis=True, keepPrefix=True,
+        run = hip.lanczos_run(Hd, device_columns(hip, B[:K], *LO), Z8, keepBasis=True, keepPrefix=True,
                               basisBytes=nseg * seg * slot_bytes(n, K) + 8)
         assert run.converged and run.basis_vectors == [p] and run.basis_kept == [False]
         qs = arrays(run.combine(lf.filter_coefficients(run.scalars, Z8, W8)))
         assert run.products_pass2 == [run.products_pass1[0] - p] and run.products_pass2[0] > 0
         run.release()
-    if name not in _spectra:
-        _spectra[name] = np.linalg.eigh(Hh.toarray())
-    lam, U = _spectra[name]
+    lam, U = spectrum(name, Hh)
     for r in range(K):
-        its, xnorms = twin(name, r, Hh, B[r], rtol, atol)
+        its, est, conv, xnorms = twin((name, r), Hh, B[r], Z8, rtol, atol, 1.0)
+        assert conv.all()
         diff = [int(d) - int(t) for d, t in zip(run.scalars[r].iterations, its)]
         print(f"STEPS {name} K={K} variant=2 prefix column={r} twin={list(map(int, its))} device-twin={diff}")
         assert max(abs(d) for d in diff) <= STEP_DIFFERENCE_BOUND, (name, r, diff)
@@ -342,7 +241,7 @@ def test_sixteen_columns_group_by_group(hip, problems, monkeypatch):
         return inner(H, cols, *args, **kw)
 
     with block_variant(Hd, 1):
-        cols = device_columns(hip, B[:16])
+        cols = device_columns(hip, B[:16], *LO)
         want = arrays(hip.lanczos_filter(Hd, cols, Z8, W8, basis="recompute"))
         monkeypatch.setattr(lf, "lanczos_run", recording)
         got = arrays(hip.lanczos_filter(Hd, cols, Z8, W8, basis="keep", prefix=True, basisBytes=budget))
@@ -413,4 +312,4 @@ def test_the_option_needs_the_kept_basis(hip, problems):
         hip.feastDiagonalization(Hd, [hip.HipVector(b.copy(), o) for b in B[:2]], 16, "legendre", -0.21, 0.21, 1e-4, 1,
                                  writeOut=False)
     with pytest.raises(ValueError, match="[Pp]refix"):
-        hip.lanczos_run(Hd, device_columns(hip, B[:2]), Z8, keepPrefix=True)
+        hip.lanczos_run(Hd, device_columns(hip, B[:2], *LO), Z8, keepPrefix=True)
