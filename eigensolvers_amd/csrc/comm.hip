@@ -575,7 +575,7 @@ extern "C" int hipeig_phase_get(hipeig_ctx* c, double out[8]) {
 // reps SUM all-reduces of `count` doubles back to back on the compute stream; *ms_each = average time of one.
 extern "C" int hipeig_comm_bench_allreduce(hipeig_ctx* c, int count, int reps, double* ms_each) {
   HIPEIG_REQUIRE(count >= 1 && count <= 1024 && reps >= 1 && ms_each, "bad arguments");
-  double* buf = c->d_scalars + 2048;
+  double* buf = c->d_scalars + SC_COMM;
   HIPEIG_CHECK(hipMemsetAsync(buf, 0, (size_t)count * sizeof(double), c->stream));
   if (hipeig_allreduce_sum(c, buf, count)) return 4;                   // warm-up
   HIPEIG_CHECK(hipEventRecord(c->ev0, c->stream));

@@ -35,6 +35,54 @@ struct GatherLayout {
   __host__ __device__ int64_t total() const { return cbase[nchunks]; }
 };
 
+// ---- the scalar area: ctx->d_scalars and its pinned mirror ctx->h_scalars, HIPEIG_SCALARS doubles each --------------
+// Every offset any translation unit uses, with its length in doubles.  [0, SC_GATHER_OFFS) of the device side holds the
+// results of reductions (dot products, coefficients); the regions below it belong to one feature each.
+enum : int {
+  HIPEIG_SCALARS = 4096,
+  // device side (d_scalars)
+  SC_RECORDS = 8,          SC_RECORDS_LEN = 4,          // hipeig_orthonormalize's MGS sweep: two total records of 2, used alternately
+  // first row of every rank, as int64 (operator set-up).  spmv.hip spells this offset as the literal 1024: its bytes are
+  // part of the signature that ties profiles/pmc_current.json to the sweep sources (bench.py, kernel_signature).
+  SC_GATHER_OFFS = 1024,   SC_GATHER_OFFS_LEN = HIPEIG_MAX_RANKS + 1,
+  SC_COMM = 2048,          SC_COMM_LEN = 32,            // block MINRES's all-reduce records (minres_block.hip)
+  SC_COMM_BENCH_LEN = 1024,                             // hipeig_comm_bench_allreduce takes up to this much from SC_COMM
+  SC_ARN_RESULT = 2560,    SC_ARN_RESULT_LEN = 1040,    // the Arnoldi step's result record / the projection's coefficients
+  SC_MINRES_TOT = 3072,    SC_MINRES_TOT_LEN = 8,       // MINRES and shifted MINRES: totals of the iteration's reductions
+  SC_ARN_TOTALS = 3200,    SC_ARN_TOTALS_LEN = 64,      // blocked sweep: two total records of 32, used alternately
+  SC_ARN_RED = 3600,       SC_ARN_RED_LEN = 2,          // partitioned sweep: the value(s) handed to the all-reduce
+  // host side (h_scalars): [0, SH_SLOTS) mirrors results; the split Arnoldi step reports into 16 pinned slots
+  SH_SLOTS = 2048,         SH_SLOT_LEN = 128,           SH_NSLOTS = 16,
+  // what a call may ask of the Arnoldi result record (doubles); the limits on m in arnoldi.hip follow from these
+  ARN_STEP_MAX_SCALARS = 1002,                          // a step's [nb^2, h.., na^2]: m <= 1000 real, 500 pair
+  ARN_PROJECT_MAX_SCALARS = 1024,                       // a projection's coefficients: m <= 1024 real, 512 pair
+  ARN_BLOCKED_MAX_COLS_REAL = 600, ARN_BLOCKED_MAX_COLS_PAIR = 250,     // blocked step: the record ends below SC_ARN_TOTALS
+};
+#define SC_DISJOINT(a, alen, b, blen) ((a) + (alen) <= (b) || (b) + (blen) <= (a))
+static_assert(SC_RECORDS + SC_RECORDS_LEN <= SC_GATHER_OFFS && SC_GATHER_OFFS + SC_GATHER_OFFS_LEN <= SC_COMM &&
+              SC_COMM + SC_COMM_BENCH_LEN <= HIPEIG_SCALARS && SC_ARN_RESULT + SC_ARN_RESULT_LEN <= HIPEIG_SCALARS &&
+              SC_MINRES_TOT + SC_MINRES_TOT_LEN <= HIPEIG_SCALARS && SC_ARN_TOTALS + SC_ARN_TOTALS_LEN <= HIPEIG_SCALARS &&
+              SC_ARN_RED + SC_ARN_RED_LEN <= HIPEIG_SCALARS && SH_SLOTS + SH_NSLOTS * SH_SLOT_LEN <= HIPEIG_SCALARS,
+              "a region of the scalar area does not fit");
+// Live together: the operator's set-up scratch, block MINRES's records and any one solver's regions; within the Arnoldi
+// step its result record, the all-reduce scratch and - blocked sweep only - the total records.
+static_assert(SC_DISJOINT(SC_COMM, SC_COMM_LEN, SC_ARN_RESULT, SC_ARN_RESULT_LEN) &&
+              SC_DISJOINT(SC_COMM, SC_COMM_LEN, SC_MINRES_TOT, SC_MINRES_TOT_LEN) &&
+              SC_DISJOINT(SC_ARN_RESULT, SC_ARN_RESULT_LEN, SC_ARN_RED, SC_ARN_RED_LEN) &&
+              SC_DISJOINT(SC_ARN_TOTALS, SC_ARN_TOTALS_LEN, SC_ARN_RED, SC_ARN_RED_LEN) &&
+              SC_DISJOINT(SC_MINRES_TOT, SC_MINRES_TOT_LEN, SC_ARN_TOTALS, SC_ARN_TOTALS_LEN) &&
+              SC_ARN_RESULT + ARN_BLOCKED_MAX_COLS_REAL + 2 <= SC_ARN_TOTALS &&
+              SC_ARN_RESULT + 2 * ARN_BLOCKED_MAX_COLS_PAIR + 2 <= SC_ARN_TOTALS &&
+              ARN_STEP_MAX_SCALARS <= SC_ARN_RESULT_LEN && ARN_PROJECT_MAX_SCALARS <= SC_ARN_RESULT_LEN &&
+              ARN_STEP_MAX_SCALARS <= SH_SLOTS && ARN_PROJECT_MAX_SCALARS <= SH_SLOTS,
+              "regions of the scalar area that are live together overlap");
+// Allowed to overlap:
+//  - SC_ARN_RESULT and SC_MINRES_TOT (and, for the sequential and partitioned sweeps, SC_ARN_TOTALS): a solve is either
+//    MINRES or GCROT, and only the blocked sweep, whose record is held below SC_ARN_TOTALS, uses the total records;
+//  - SC_COMM_BENCH_LEN past SC_COMM_LEN: the all-reduce bench is a measurement call that runs alone;
+//  - on the host, hipeig_lincomb_block stages coefficients over the whole mirror: its callers have collected every
+//    pinned slot before they combine.
+
 void hipeig_set_error(const char* fmt, ...);
 
 #define HIPEIG_CHECK(expr)                                                              \
@@ -159,6 +207,7 @@ struct LfPoolEntry {
   size_t bytes;
 };
 void hipeig_lf_pool_clear(hipeig_ctx* c);   // lanczos_filter.hip: hipFree every pooled segment
+void arnoldi_release(hipeig_ctx* c);        // arnoldi.hip: side streams, their events and workspaces, the batch items
 
 // One blocked copy of the operator (TCOO, TCOO-W, the pair copy of TCOO-W, TCOO-B): the local rows cut into units of
 // `rw` rows, the columns into windows of 2^wbits; the non-zeros of (unit, window) tile t, stored as

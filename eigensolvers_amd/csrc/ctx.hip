@@ -40,7 +40,7 @@ extern "C" int hipeig_ctx_create(int device, hipeig_ctx** out) {
   HIPEIG_CHECK(hipMalloc((void**)&c->d_group_partials, (size_t)32 * 1024 * sizeof(double)));
   c->partials_doubles = (size_t)HIPEIG_MAX_PARTIALS * HIPEIG_MAX_COLS * HIPEIG_MAX_COLS * 2;   // 8 MiB
   HIPEIG_CHECK(hipMalloc((void**)&c->d_partials, c->partials_doubles * sizeof(double)));
-  c->scalars_doubles = 4096;
+  c->scalars_doubles = HIPEIG_SCALARS;
   HIPEIG_CHECK(hipMalloc((void**)&c->d_scalars, c->scalars_doubles * sizeof(double)));
   HIPEIG_CHECK(hipHostMalloc((void**)&c->h_scalars, c->scalars_doubles * sizeof(double),
                              hipHostMallocDefault));
@@ -76,11 +76,7 @@ extern "C" int hipeig_ctx_destroy(hipeig_ctx* c) {
   hipFree(c->d_partials);
   hipFree(c->d_scalars);
   hipHostFree(c->h_scalars);
-  if (c->h_arn_items) hipHostFree(c->h_arn_items);
-  for (int k = 0; k < 16; ++k) if (c->arn_stream[k]) { hipStreamSynchronize(c->arn_stream[k]); hipStreamDestroy(c->arn_stream[k]); }
-  for (int k = 0; k < 16; ++k) if (c->ev_arn_in[k]) hipEventDestroy(c->ev_arn_in[k]);
-  if (c->d_arn_ws) hipFree(c->d_arn_ws);
-  if (c->d_arn_cnt) hipFree(c->d_arn_cnt);
+  arnoldi_release(c);
   hipFree(c->d_ptrs);
   hipHostFree(c->h_ptrs);
   hipFree(c->d_mr_state);

@@ -338,7 +338,7 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
   double* pA = c->d_partials;
   double* pC = c->d_partials + HIPEIG_WIDE_PARTIALS;
   double* pD = c->d_partials + 2 * HIPEIG_WIDE_PARTIALS;
-  double* tot = c->d_scalars + 3072;                         // [0] <v,y>, [1] <x,x> (one all-reduce record), [2] <y,y>, [4..5] end-of-solve flush
+  double* tot = c->d_scalars + SC_MINRES_TOT;                         // [0] <v,y>, [1] <x,x> (one all-reduce record), [2] <y,y>, [4..5] end-of-solve flush
   unsigned* cntA = c->d_counters + 0;
   unsigned* cntC = c->d_counters + HIPEIG_TICKET_WORDS;
   unsigned* cntD = c->d_counters + 2 * HIPEIG_TICKET_WORDS;

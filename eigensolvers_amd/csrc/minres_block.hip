@@ -309,7 +309,7 @@ static int minres_block_impl(hipeig_ctx* c, hipeig_csr* A, double sigma, double 
   const bool dist = c->collectives != 0;
   // row-partitioned run: reduced records of 8 - [0..7] <v,y>, [8..15] <x,x> (ONE all-reduce), [16..23] / [24..31] the
   // end-of-solve flush
-  double* red = c->d_scalars + 2048;
+  double* red = c->d_scalars + SC_COMM;
   MinresArgs a;
   a.sigma = sigma; a.sign = sign; a.rtol = rtol; a.maxiter = maxiter; a.sC = 0;
   const int nPA = gA * nsweepA;

@@ -342,7 +342,7 @@ extern "C" int hipeig_minres_shifts(hipeig_ctx* c, hipeig_csr* A, double sign, i
   HIPEIG_REQUIRE(nPA <= HIPEIG_WIDE_PARTIALS, "too many sweeps for the partial-sum buffer");
   double* pA = c->d_partials;
   double* pC = c->d_partials + HIPEIG_WIDE_PARTIALS;
-  double* tot = c->d_scalars + 3072;                           // [0] <v,w>, [1] <w,w>
+  double* tot = c->d_scalars + SC_MINRES_TOT;                           // [0] <v,w>, [1] <w,w>
   unsigned* cntA = c->d_counters + 0;
   unsigned* cntC = c->d_counters + HIPEIG_TICKET_WORDS;
   HIPEIG_CHECK(hipMemsetAsync(tot, 0, 8 * sizeof(double), c->stream));

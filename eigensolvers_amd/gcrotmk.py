@@ -23,6 +23,73 @@ from scipy.linalg import lstsq, qr_insert
 from . import _lib
 
 
+_PP, _DP = C.POINTER(C.c_void_p), C.POINTER(C.c_double)
+
+
+def _name(stem, pair):
+    return ("hipeig_pair_" if pair else "hipeig_") + stem
+
+
+def _tables(vs, pair):
+    """The vectors ``vs`` (None: an empty entry) as pointer tables of at least one entry: one table, or (re, im) for pairs."""
+    cols = [[v and v[k].ptr for v in vs] for k in (0, 1)] if pair else [[v and v.ptr for v in vs]]
+    return [C.cast((C.c_void_p * max(len(t), 1))(*t), _PP) for t in cols]
+
+
+def _parts(w, pair):
+    return [w[0].ptr, w[1].ptr] if pair else [w.ptr]
+
+
+def _scalars(m, pair, extra):
+    out = np.empty((2 if pair else 1) * m + extra)
+    return out, out.ctypes.data_as(_DP)
+
+
+def _unpack(out, m, pair, step=True):
+    """A step's scalars [nb^2, h_0 .. h_{m-1}, na^2] -> (norm before, coefficients, norm after); a projection's are the
+    coefficients alone.  Pairs carry complex coefficients as (re, im)."""
+    h = out[1:-1] if step else out
+    h = h[0::2] + 1j * h[1::2] if pair else h
+    return (float(np.sqrt(out[0])), h, float(np.sqrt(out[-1]))) if step else h
+
+
+def _mgs_project(r, pair, vs, w):
+    out, ptr = _scalars(len(vs), pair, 0)
+    if len(vs):
+        _lib.call(_name("mgs_project", pair), r.h, r.n, len(vs), *_tables(vs, pair), *_parts(w, pair), ptr)
+    return _unpack(out, len(vs), pair, step=False)
+
+
+def _arnoldi_step(r, pair, cols_per_pass, vs, w):
+    out, ptr = _scalars(len(vs), pair, 2)
+    _lib.call(_name("arnoldi_step_p", pair), r.h, r.n, len(vs), *_tables(vs, pair), *_parts(w, pair), ptr, cols_per_pass)
+    return _unpack(out, len(vs), pair)
+
+
+def _arnoldi_begin(r, pair, cols_per_pass, vs, w, slot):
+    _lib.call(_name("arnoldi_step_begin", pair), r.h, r.n, len(vs), *_tables(vs, pair), *_parts(w, pair), cols_per_pass, int(slot))
+
+
+def _arnoldi_end(r, pair, m, slot):
+    out, ptr = _scalars(m, pair, 2)
+    _lib.call("hipeig_arnoldi_step_end", r.h, int(slot), out.size, ptr)
+    return _unpack(out, m, pair)
+
+
+def _arnoldi_begin_batch(r, pair, reqs):
+    """The steps ``reqs = [(columns, w), ...]`` of up to 16 right-hand sides in one launch, a workgroup each (slots
+    0, 1, ...; collect with ``arnoldi_end``).  Returns False, having done nothing, when the library declines (vectors
+    longer than one workgroup handles)."""
+    ms = (C.c_int * len(reqs))(*[len(vs) for vs, _ in reqs])
+    cols = [v for vs, _ in reqs for v in list(vs) + [None] * (64 - len(vs))]        # tables of 64 entries per step
+    name = _name("arnoldi_step_batch_begin", pair)
+    rc = getattr(_lib.load(), name)(r.h, r.n, len(reqs), ms, *_tables(cols, pair), *_tables([w for _, w in reqs], pair))
+    if rc == 5:
+        return False
+    _lib.check(rc, name)
+    return True
+
+
 class _Ops:
     """Thin helpers over the C ABI for raw device buffers of one length."""
 
@@ -61,34 +128,19 @@ class _Ops:
 
     def mgs_project(self, vs, w):
         """Sequential MGS of w against vs on the device; returns the coefficients."""
-        out = np.empty(len(vs))
-        if len(vs):
-            tab = (C.c_void_p * len(vs))(*[v.ptr for v in vs])
-            _lib.call("hipeig_mgs_project", self.h, self.n, len(vs), C.cast(tab, C.POINTER(C.c_void_p)), w.ptr,
-                      out.ctypes.data_as(C.POINTER(C.c_double)))
-        return out
+        return _mgs_project(self, False, vs, w)
 
     def arnoldi_step(self, vs, w):
         """||w||, sequential MGS of w against vs, ||w|| again and w /= ||w|| (when finite) in ONE call
         and one host round trip; returns (norm before, coefficients, norm after)."""
-        m = len(vs)
-        out = np.empty(m + 2)
-        tab = (C.c_void_p * max(m, 1))(*[v.ptr for v in vs])
-        _lib.call("hipeig_arnoldi_step_p", self.h, self.n, m, C.cast(tab, C.POINTER(C.c_void_p)), w.ptr,
-                  out.ctypes.data_as(C.POINTER(C.c_double)), self.cols_per_pass)
-        return float(np.sqrt(out[0])), out[1:m + 1], float(np.sqrt(out[m + 1]))
+        return _arnoldi_step(self, False, self.cols_per_pass, vs, w)
 
     def arnoldi_begin(self, vs, w, slot):
         """Enqueue the step without waiting for its scalars (pinned slot ``slot``); ``arnoldi_end`` collects them."""
-        m = len(vs)
-        tab = (C.c_void_p * max(m, 1))(*[v.ptr for v in vs])
-        _lib.call("hipeig_arnoldi_step_begin", self.h, self.n, m, C.cast(tab, C.POINTER(C.c_void_p)), w.ptr,
-                  self.cols_per_pass, int(slot))
+        _arnoldi_begin(self, False, self.cols_per_pass, vs, w, slot)
 
     def arnoldi_end(self, m, slot):
-        out = np.empty(m + 2)
-        _lib.call("hipeig_arnoldi_step_end", self.h, int(slot), m + 2, out.ctypes.data_as(C.POINTER(C.c_double)))
-        return float(np.sqrt(out[0])), out[1:m + 1], float(np.sqrt(out[m + 1]))
+        return _arnoldi_end(self, False, m, slot)
 
     SPLIT_MAX_COLS = 124         # m + 2 doubles must fit a pinned slot (hipeig.h)
     BATCH_MAX_N = 8192           # lengths at which a step is ONE workgroup: several steps share a launch
@@ -96,22 +148,7 @@ class _Ops:
 
     @staticmethod
     def arnoldi_begin_batch(opss, reqs):
-        """The steps ``reqs = [(columns, w), ...]`` of up to 16 right-hand sides in one launch, a workgroup each (slots
-        0, 1, ...; collect with ``arnoldi_end``).  Returns False, having done nothing, when the library declines (vectors
-        longer than one workgroup handles)."""
-        cnt, r = len(reqs), opss[0]
-        ms = (C.c_int * cnt)(*[len(vs) for vs, _ in reqs])
-        tab = (C.c_void_p * (64 * cnt))()
-        for i, (vs, _) in enumerate(reqs):
-            for j, v in enumerate(vs):
-                tab[64 * i + j] = v.ptr
-        ws = (C.c_void_p * cnt)(*[w.ptr for _, w in reqs])
-        PP = C.POINTER(C.c_void_p)
-        rc = getattr(_lib.load(), "hipeig_arnoldi_step_batch_begin")(r.h, r.n, cnt, ms, C.cast(tab, PP), C.cast(ws, PP))
-        if rc == 5:
-            return False
-        _lib.check(rc, "hipeig_arnoldi_step_batch_begin")
-        return True
+        return _arnoldi_begin_batch(opss[0], False, reqs)
 
     def combine(self, coeffs, vecs):
         """sum_i coeffs[i] * vecs[i] in one pass."""
@@ -187,38 +224,16 @@ class _PairOps:
         return out
 
     def mgs_project(self, vs, w):
-        out = np.empty(2 * len(vs))
-        if len(vs):
-            tr = (C.c_void_p * len(vs))(*[v[0].ptr for v in vs])
-            ti = (C.c_void_p * len(vs))(*[v[1].ptr for v in vs])
-            _lib.call("hipeig_pair_mgs_project", self.r.h, self.r.n, len(vs), C.cast(tr, C.POINTER(C.c_void_p)),
-                      C.cast(ti, C.POINTER(C.c_void_p)), w[0].ptr, w[1].ptr, out.ctypes.data_as(C.POINTER(C.c_double)))
-        return out[0::2] + 1j * out[1::2]
+        return _mgs_project(self.r, True, vs, w)
 
     def arnoldi_step(self, vs, w):
-        m = len(vs)
-        out = np.empty(2 * m + 2)
-        tr = (C.c_void_p * max(m, 1))(*[v[0].ptr for v in vs])
-        ti = (C.c_void_p * max(m, 1))(*[v[1].ptr for v in vs])
-        _lib.call("hipeig_pair_arnoldi_step_p", self.r.h, self.r.n, m, C.cast(tr, C.POINTER(C.c_void_p)),
-                  C.cast(ti, C.POINTER(C.c_void_p)), w[0].ptr, w[1].ptr, out.ctypes.data_as(C.POINTER(C.c_double)),
-                  self.cols_per_pass)
-        h = out[1:2 * m + 1]
-        return float(np.sqrt(out[0])), h[0::2] + 1j * h[1::2], float(np.sqrt(out[2 * m + 1]))
+        return _arnoldi_step(self.r, True, self.cols_per_pass, vs, w)
 
     def arnoldi_begin(self, vs, w, slot):
-        """Enqueue the step without waiting for its scalars (pinned slot ``slot``); ``arnoldi_end`` collects them."""
-        m = len(vs)
-        tr = (C.c_void_p * max(m, 1))(*[v[0].ptr for v in vs])
-        ti = (C.c_void_p * max(m, 1))(*[v[1].ptr for v in vs])
-        _lib.call("hipeig_pair_arnoldi_step_begin", self.r.h, self.r.n, m, C.cast(tr, C.POINTER(C.c_void_p)),
-                  C.cast(ti, C.POINTER(C.c_void_p)), w[0].ptr, w[1].ptr, self.cols_per_pass, int(slot))
+        _arnoldi_begin(self.r, True, self.cols_per_pass, vs, w, slot)
 
     def arnoldi_end(self, m, slot):
-        out = np.empty(2 * m + 2)
-        _lib.call("hipeig_arnoldi_step_end", self.r.h, int(slot), 2 * m + 2, out.ctypes.data_as(C.POINTER(C.c_double)))
-        h = out[1:2 * m + 1]
-        return float(np.sqrt(out[0])), h[0::2] + 1j * h[1::2], float(np.sqrt(out[2 * m + 1]))
+        return _arnoldi_end(self.r, True, m, slot)
 
     SPLIT_MAX_COLS = 62          # 2m + 2 doubles must fit a pinned slot (hipeig.h)
     BATCH_MAX_N = 8192           # lengths at which a step is ONE workgroup: several steps share a launch
@@ -226,24 +241,7 @@ class _PairOps:
 
     @staticmethod
     def arnoldi_begin_batch(opss, reqs):
-        """The steps ``reqs = [(columns, w), ...]`` of up to 16 right-hand sides in one launch, a workgroup each (slots
-        0, 1, ...; collect with ``arnoldi_end``).  Returns False, having done nothing, when the library declines (vectors
-        longer than one workgroup handles)."""
-        cnt, r = len(reqs), opss[0].r
-        ms = (C.c_int * cnt)(*[len(vs) for vs, _ in reqs])
-        tr, ti = (C.c_void_p * (64 * cnt))(), (C.c_void_p * (64 * cnt))()
-        for i, (vs, _) in enumerate(reqs):
-            for j, v in enumerate(vs):
-                tr[64 * i + j], ti[64 * i + j] = v[0].ptr, v[1].ptr
-        wr = (C.c_void_p * cnt)(*[w[0].ptr for _, w in reqs])
-        wi = (C.c_void_p * cnt)(*[w[1].ptr for _, w in reqs])
-        PP = C.POINTER(C.c_void_p)
-        rc = getattr(_lib.load(), "hipeig_pair_arnoldi_step_batch_begin")(r.h, r.n, cnt, ms, C.cast(tr, PP), C.cast(ti, PP),
-                                                                          C.cast(wr, PP), C.cast(wi, PP))
-        if rc == 5:
-            return False
-        _lib.check(rc, "hipeig_pair_arnoldi_step_batch_begin")
-        return True
+        return _arnoldi_begin_batch(opss[0].r, True, reqs)
 
     def combine(self, coeffs, vecs):
         cf = np.asarray(coeffs, dtype=np.complex128)

@@ -328,6 +328,75 @@ def test_mgs_projection_against_the_high_precision_reference(hip, pair, n):
     worst.report()
 
 
+# ---------------------------------------------------------------- the partitioned sweep (an all-reduce per column)
+@pytest.mark.parametrize("P", [2, 3])
+@pytest.mark.parametrize("pair", [False, True], ids=["real", "pair"])
+def test_partitioned_arnoldi_step_on_loopback_ranks(hip, pair, P):
+    """The row-partitioned form of the step and of the projection (arnoldi.hip, arnoldi_partitioned: dot kernel,
+    one-workgroup reduce, all-reduce, update kernel per column) on P loopback ranks with ragged row ranges of n = 1003:
+    every rank uploads its rows and calls arnoldi_step with cols_per_pass 1 and 4 (a partitioned run takes the same
+    sweep for both) and mgs_project.  Every rank returns the same scalars bit for bit, cols_per_pass 4 equals 1 bit for
+    bit, and the concatenated w with the scalars is within the module's bounds of the extended-precision sweep."""
+    from eigensolvers_amd.distributed import LoopbackGroup, row_range
+    from eigensolvers_amd.gcrotmk import _Ops, _PairOps
+    n = 1003
+    rng = np.random.default_rng(1003 + 10 * P + pair)
+    cases = []
+    for skew in (False, True):
+        for m in (0, 1, 5, 17):
+            V = _orthonormal(rng, n, m, pair)
+            if skew and m >= 3:
+                V = _skewed(V, pair)
+            a = rng.standard_normal(m) + (1j * rng.standard_normal(m) if pair else 0.0)
+            r = rng.standard_normal(n) + (1j * rng.standard_normal(n) if pair else 0.0)
+            cases.append((skew, m, V, (V.T @ a if m else 0.0) + 1e-8 * r))
+    grp = LoopbackGroup(P)
+
+    def body(rank, ctx):
+        assert ctx.collectives
+        b, e = row_range(n, P, rank)
+        ops = {cols: (_PairOps if pair else _Ops)(ctx, e - b, cols) for cols in (1, 4)}
+        out = []
+        for skew, m, V, w in cases:
+            Vd = _up_cols(ctx, V[:, b:e], pair)
+            got = {}
+            for cols in (1, 4):
+                wd = _up_w(ctx, w[b:e], pair)
+                nb, h, na = ops[cols].arnoldi_step(Vd, wd)
+                got[cols] = (nb, np.array(h), na, _down_w(ctx, wd, pair))
+            wd = _up_w(ctx, w[b:e], pair)
+            got["mgs"] = (np.array(ops[1].mgs_project(Vd, wd)), _down_w(ctx, wd, pair))
+            out.append(got)
+        return out
+
+    try:
+        res = grp.run(body)
+    finally:
+        grp.close()
+    worst = _Worst(f"partitioned {'pair' if pair else 'real'} P={P}")
+    for k, (skew, m, V, w) in enumerate(cases):
+        what = f"m={m} skew={skew}"
+        for o in res:
+            for cols in (1, 4):
+                assert o[k][cols][0] == res[0][k][1][0] and o[k][cols][2] == res[0][k][1][2], f"{what} cols={cols}: norms differ"
+                np.testing.assert_array_equal(o[k][cols][1], res[0][k][1][1], err_msg=f"{what} cols={cols}: coefficients differ")
+                np.testing.assert_array_equal(o[k][cols][3], o[k][1][3], err_msg=f"{what}: w of cols_per_pass 4 differs from 1")
+            np.testing.assert_array_equal(o[k]["mgs"][0], res[0][k]["mgs"][0], err_msg=f"{what}: projection coefficients differ")
+        vn = np.array([float(hp.nrm2(v)) for v in V])
+        group = "skew" if skew else "orth"
+        nb, h, na, _ = res[0][k][1]
+        _check_step(worst, f"step {group}", f"step {what}", (nb, h, na, np.concatenate([o[k][1][3] for o in res])),
+                    hp.mgs(V, w), vn)
+        wv = np.concatenate([o[k]["mgs"][1] for o in res])
+        if m == 0:
+            np.testing.assert_array_equal(wv, w)                      # nothing to project against: w untouched
+            continue
+        nb_r, h_r, na_r, w_r = hp.mgs(V, w, normalise=False)
+        _check_step(worst, f"project {group}", f"project {what}", (float(nb_r), res[0][k]["mgs"][0], float(na_r), wv),
+                    (nb_r, h_r, na_r, w_r), vn, normalised=False)
+    worst.report()
+
+
 # ---------------------------------------------------------------- block complex-shift product
 @pytest.mark.parametrize("width", [4, 8])
 @pytest.mark.parametrize("variant", [1, 2])
