@@ -110,6 +110,7 @@ SIGNATURES = {
     "hipeig_lanczos_combine": [_P, _P, _P, C.c_int, _PP, _IP, C.POINTER(_DP), C.POINTER(_DP), C.c_int, C.POINTER(_DP), _PP,
                                _DP],
     "hipeig_lanczos_basis_info": [_P, _P, _I64P],
+    "hipeig_lanczos_basis_element_bytes": [_P, _P, _IP],
     "hipeig_lanczos_basis_release": [_P, _P],
     "hipeig_csr_set_block_variant": [_P, C.c_int],
     "hipeig_csr_block_info": [_P, _I64P],

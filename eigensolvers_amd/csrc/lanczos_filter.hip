@@ -20,7 +20,9 @@
 // Keep mode (basis_mode 1): pass 1 leaves every r_k in a slot of a basis in device memory instead of a ring of three, and
 // pass 2 is one stream over the slots - see "kept basis" below.  Prefix mode (basis_mode 2): a basis that outgrows its
 // byte budget keeps the first p vectors, and pass 2 is the stream for the terms i < p - 1 plus the recurrence from step
-// p - 1.  The three are one host path with a plan - see "pass 2, host side".
+// p - 1.  The three are one host path with a plan - see "pass 2, host side".  basis_mode 3 / 4: modes 1 / 2 with the basis
+// stored in fp32 - the recurrence stays in the fp64 ring and KC leaves a rounded copy of every vector in its slot - see
+// "fp32 basis" below.
 #include <limits.h>
 #include <math.h>
 #include "spmm_device.h"
@@ -122,11 +124,13 @@ __device__ __forceinline__ void lf_reduce_pairs(double a0, double a1, double* ld
   }
 }
 
-// W -= (alpha / beta_k) R_k per column, and the partials of <w, w>.
-template <int K>
+// W -= (alpha / beta_k) R_k per column, and the partials of <w, w>.  S32: the finished w also goes, rounded to fp32
+// (round to nearest even), to w32 - a slot of an fp32 basis - in one 8-byte store of the thread's column pair.
+template <int K, bool S32 = false>
 __global__ void __launch_bounds__(HIPEIG_BLOCK)
 lf_kc_kernel(int64_t n, const LfState* __restrict__ S, const double* __restrict__ pA, int nA,
-             const double* __restrict__ rk, double* __restrict__ w, double* __restrict__ partials) {
+             const double* __restrict__ rk, double* __restrict__ w, double* __restrict__ partials,
+             float* __restrict__ w32 = nullptr) {
   __shared__ double red[HIPEIG_BLOCK / 64 * K];
   __shared__ double sh_c[K];
   if (S->done) return;
@@ -148,9 +152,20 @@ lf_kc_kernel(int64_t n, const LfState* __restrict__ S, const double* __restrict_
     double2 wv = w2[t];
     wv.x = fma(-c0, rv.x, wv.x); wv.y = fma(-c1, rv.y, wv.y);
     w2[t] = wv;
+    if (S32) reinterpret_cast<float2*>(w32)[t] = make_float2((float)wv.x, (float)wv.y);
     a0 = fma(wv.x, wv.x, a0); a1 = fma(wv.y, wv.y, a1);
   }
   lf_reduce_pairs<K>(a0, a1, red, partials + (size_t)blockIdx.x * K);
+}
+
+// The packed b, slot 0 of an fp32 basis, rounded once: a column pair per thread, as above.
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+lf_round_kernel(int64_t n2, const double2* __restrict__ r, float2* __restrict__ r32) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n2; t += stride) {
+    const double2 v = r[t];
+    r32[t] = make_float2((float)v.x, (float)v.y);
+  }
 }
 
 // One workgroup of 256: thread (column = t / 32, shift = t % 32) advances that shift's rotation with the expressions of
@@ -326,13 +341,24 @@ static int lf_width(int k) {
 // in HBM at no extra byte of traffic, and pass 2 becomes one stream over them (lf_basis_combine_kernel) - pass 1's vectors
 // themselves, whichever sweep produced them.  Slots are carved from segments of seg_slots slots, allocated while the run
 // advances; a fresh slot is fully written by the sweep (every row, padding columns as 0) before anything reads it.
+//
+// fp32 basis (basis_mode 3 / 4, elem_bytes = 4): pass 2 only forms q = sum_i g_i v_i, so the copy it streams over may be
+// narrower than the vectors of the recurrence.  Pass 1 runs in the ring of three exactly as mode 0 - the same kernels on
+// the same operands, so the same scalars - and KC's S32 variant leaves step k's finished w, rounded, in slot k + 1 (slot 0:
+// the packed b, lf_round_kernel): 4 n K more bytes written per step.  A slot is nb floats; KC writes the n K elements the
+// stream reads (padding and finished columns as 0).  A prefix of such a basis cannot restart pass 2's recurrence from
+// its slots - rounded start vectors would no longer repeat pass 1's arithmetic - so the basis owns two fp64 hand-over
+// vectors: r_{p-1} and r_{p-2}, copied out of the ring in stream order before step p - 1 is enqueued.  They are
+// allocations of their own, outside the byte budget (which is the segments') and outside the pool, and count as held.
 struct hipeig_lanczos_basis {
   int K, k, seg_slots, nseg, seg_cap;
-  int64_t n, nb, nrows;                                       // nb: doubles per slot; nrows: the operator's
+  int elem_bytes;                                             // 8, or 4: slots of nb floats
+  int64_t n, nb, nrows;                                       // nb: elements per slot; nrows: the operator's
   size_t seg_bytes;
   int steps[BCOO_KMAX];                                       // vectors kept per column: v_0 .. v_{steps - 1}
   int ran[BCOO_KMAX];                                         // steps the column ran: more than `steps` behind a prefix
   double** seg;
+  double* hand[2];                                            // fp32 prefix: r_{p-1}, r_{p-2} in fp64 (nb doubles each), else null
 };
 
 void hipeig_lf_pool_clear(hipeig_ctx* c) {
@@ -373,8 +399,11 @@ static void lf_pool_give(hipeig_ctx* c, double* p, size_t bytes) {
 }
 
 static inline double* lf_slot(const hipeig_lanczos_basis* B, int i) {
-  return B->seg[i / B->seg_slots] + (int64_t)(i % B->seg_slots) * B->nb;
+  char* s = reinterpret_cast<char*>(B->seg[i / B->seg_slots]) + (int64_t)(i % B->seg_slots) * B->nb * B->elem_bytes;
+  return reinterpret_cast<double*>(s);
 }
+
+static inline float* lf_slot32(const hipeig_lanczos_basis* B, int i) { return reinterpret_cast<float*>(lf_slot(B, i)); }
 
 // One more segment, unless it would exceed the byte budget or the device has no room: 0 = added.
 static int lf_basis_grow(hipeig_ctx* c, hipeig_lanczos_basis* B, int64_t budget) {
@@ -397,9 +426,17 @@ static void lf_basis_trim(hipeig_ctx* c, hipeig_lanczos_basis* B, int from) {
   while (B->nseg > from) lf_pool_give(c, B->seg[--B->nseg], B->seg_bytes);
 }
 
+static void lf_basis_drop_hand(hipeig_ctx* c, hipeig_lanczos_basis* B) {
+  for (int q = 0; q < 2; ++q) {
+    if (B->hand[q]) (void)hipFree(B->hand[q]);               // not pooled: a vector can never serve as a segment
+    B->hand[q] = nullptr;
+  }
+}
+
 static void lf_basis_free(hipeig_ctx* c, hipeig_lanczos_basis* B) {
   if (!B) return;
   lf_basis_trim(c, B, 0);
+  lf_basis_drop_hand(c, B);
   free(B->seg);
   free(B);
 }
@@ -409,11 +446,14 @@ static void lf_basis_free(hipeig_ctx* c, hipeig_lanczos_basis* B) {
 // prefix: when the next segment is refused the ones held stay and are written to their last slot, p = nseg * seg_slots
 // vectors; vector i >= p lives in ring buffer i % 3, so the hand-over is a choice of pointers at enqueue time - steps
 // p - 1 and p read their operands from the slots - and may fall inside a chunk.
+// elem 4: an fp32 basis.  Every vector of the recurrence lives in the ring; a slot only receives KC's rounded copy, so a
+// refused segment costs no copy (keep: the basis is freed; prefix: the slots held stay, and r_{p-1}, r_{p-2} are copied
+// from the ring to the hand-over vectors before step p - 1 - which overwrites neither - is enqueued).
 template <int K>
 static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, const double* const* b, int nshift,
                            const double* zr, const double* zi, double rtol, double atol, int maxiter, double* alphas,
                            double* betas, int* iterations, double* estimates, int* info, double* out_stats,
-                           int64_t budget, hipeig_lanczos_basis** keep, int prefix) {
+                           int64_t budget, hipeig_lanczos_basis** keep, int prefix, int elem) {
   const int64_t n = A->nrows;
   const int64_t nb = ((n * K + 31) & ~(int64_t)31);
   const int64_t ld = maxiter;
@@ -457,6 +497,7 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   const int probe = lf_env_int("HIPEIG_LF_PROBE", 0);
   // steps between two looks at the state record; kernels launched past the last column's stop return at once
   const int chunk = lf_env_int("HIPEIG_LF_CHUNK", 32);
+  const bool narrow = elem == 4;
   struct Guard {
     hipeig_ctx* c; hipeig_lanczos_basis* B;
     ~Guard() { lf_basis_free(c, B); }
@@ -464,17 +505,27 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   if (keep && !probe) {
     hipeig_lanczos_basis* B = (hipeig_lanczos_basis*)calloc(1, sizeof(hipeig_lanczos_basis));
     HIPEIG_REQUIRE(B != nullptr, "out of host memory");
-    B->K = K; B->k = k; B->n = n; B->nb = nb; B->nrows = A->nrows;
+    B->K = K; B->k = k; B->n = n; B->nb = nb; B->nrows = A->nrows; B->elem_bytes = elem;
     B->seg_slots = lf_env_int("HIPEIG_LF_SEGMENT", 32);       // slots per segment
-    B->seg_bytes = (size_t)B->seg_slots * (size_t)nb * sizeof(double);
+    B->seg_bytes = (size_t)B->seg_slots * (size_t)nb * (size_t)elem;
     kept.B = B;
-    if (lf_basis_grow(c, B, budget)) { lf_basis_free(c, B); kept.B = nullptr; }
+    bool ok = true;
+    if (narrow && prefix)                                     // the hand-over vectors, before the segments can eat their room
+      for (int q = 0; q < 2 && ok; ++q)
+        if (hipMalloc((void**)&B->hand[q], (size_t)nb * sizeof(double)) != hipSuccess) {
+          (void)hipGetLastError();
+          B->hand[q] = nullptr; ok = false;
+        }
+    if (!ok || lf_basis_grow(c, B, budget)) { lf_basis_free(c, B); kept.B = nullptr; }
   }
-  if (kept.B) {
+  if (kept.B && !narrow) {
     if (hipeig_block_pack(c, K, n, k, b, lf_slot(kept.B, 0))) return 1;
   } else {
     if (hipeig_block_pack(c, K, n, k, b, R[0])) return 1;
     HIPEIG_CHECK(hipMemsetAsync(R[1], 0, (size_t)nb * 2 * sizeof(double), c->stream));
+    if (kept.B)
+      hipLaunchKernelGGL(lf_round_kernel, dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream, n * (K / 2),
+                         reinterpret_cast<const double2*>(R[0]), reinterpret_cast<float2*>(lf_slot32(kept.B, 0)));
   }
   HIPEIG_CHECK(hipMemcpyAsync(V, h, sizeof(LfState), hipMemcpyHostToDevice, c->stream));
   if (hipeig_sync_checked(c)) return 4;                       // the pinned record is rewritten by the first copy-back
@@ -516,7 +567,7 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
 
   int steps = 0;
   int cap = INT_MAX;                                          // prefix mode, once a segment was refused: the slots held
-  auto vec = [&](int i) { return (kept.B && i < cap) ? lf_slot(kept.B, i) : R[i % 3]; };
+  auto vec = [&](int i) { return (kept.B && !narrow && i < cap) ? lf_slot(kept.B, i) : R[i % 3]; };
   while (steps < maxiter) {
     const int kend = (steps + chunk < maxiter) ? steps + chunk : maxiter;
     // the segments this chunk writes (slots up to kend) before it is enqueued; when the budget or the device says no, the
@@ -525,10 +576,12 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
     while (kept.B && cap == INT_MAX && kept.B->nseg * kept.B->seg_slots <= kend)
       if (lf_basis_grow(c, kept.B, budget)) {
         if (prefix) { cap = kept.B->nseg * kept.B->seg_slots; break; }
-        HIPEIG_CHECK(hipMemcpyAsync(R[steps % 3], lf_slot(kept.B, steps), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        if (steps)
-          HIPEIG_CHECK(hipMemcpyAsync(R[(steps + 2) % 3], lf_slot(kept.B, steps - 1), (size_t)nb * sizeof(double),
-                                      hipMemcpyDeviceToDevice, c->stream));
+        if (!narrow) {
+          HIPEIG_CHECK(hipMemcpyAsync(R[steps % 3], lf_slot(kept.B, steps), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+          if (steps)
+            HIPEIG_CHECK(hipMemcpyAsync(R[(steps + 2) % 3], lf_slot(kept.B, steps - 1), (size_t)nb * sizeof(double),
+                                        hipMemcpyDeviceToDevice, c->stream));
+        }
         lf_basis_free(c, kept.B);
         kept.B = nullptr;
       }
@@ -536,11 +589,20 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
       const int kk = probe ? 0 : steps;
       double* rk = vec(kk);
       double* w = vec(kk + 1);
-      double* rkm1 = kk ? vec(kk - 1) : kept.B ? lf_slot(kept.B, 0) : R[2];         // step 0 reads no r_{-1}
+      double* rkm1 = kk ? vec(kk - 1) : (kept.B && !narrow) ? lf_slot(kept.B, 0) : R[2];   // step 0 reads no r_{-1}
+      if (kept.B && narrow && steps == cap - 1) {             // r_{p-1} is complete; step p - 1 writes R[p % 3]
+        HIPEIG_CHECK(hipMemcpyAsync(kept.B->hand[0], R[steps % 3], (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (steps)
+          HIPEIG_CHECK(hipMemcpyAsync(kept.B->hand[1], R[(steps + 2) % 3], (size_t)nb * sizeof(double),
+                                      hipMemcpyDeviceToDevice, c->stream));
+      }
       if (!probe || probe == 1) enqueue_sweep(rk, rkm1, w);
-      if (!probe || probe == 2)
+      if (kept.B && narrow && kk + 1 < cap)
+        hipLaunchKernelGGL((lf_kc_kernel<K, true>), dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, (const LfState*)V,
+                           (const double*)pA, nPA, (const double*)rk, w, pC, lf_slot32(kept.B, kk + 1));
+      else if (!probe || probe == 2)
         hipLaunchKernelGGL(lf_kc_kernel<K>, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, (const LfState*)V,
-                           (const double*)pA, nPA, (const double*)rk, w, pC);
+                           (const double*)pA, nPA, (const double*)rk, w, pC, (float*)nullptr);
       if (!probe || probe == 3)
         hipLaunchKernelGGL(lf_scalar_kernel<K>, dim3(1), dim3(HIPEIG_BLOCK), 0, c->stream, V, sh, (const double*)pA, nPA,
                            (const double*)pC, gE, d_alphas, d_betas, (int)ld, probe ? 1 : 0);
@@ -576,6 +638,7 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   if (kept.B) {                                               // memory follows the steps taken: slots 0 .. products - 1
     const int held = products < cap ? products : cap;        // a run that stopped before the cap holds a whole basis
     lf_basis_trim(c, kept.B, (held + kept.B->seg_slots - 1) / kept.B->seg_slots);
+    if (products <= cap) lf_basis_drop_hand(c, kept.B);      // a whole basis: no recurrence will restart behind it
     *keep = kept.B;
     kept.B = nullptr;
   }
@@ -587,7 +650,7 @@ extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double
                                             int maxiter, double* alphas, double* betas, int* iterations, double* estimates,
                                             int* info, double* out_stats, int basis_mode, int64_t basis_bytes,
                                             hipeig_lanczos_basis** basis) {
-  HIPEIG_REQUIRE(basis_mode >= 0 && basis_mode <= 2, "basis mode: 0 none, 1 keep, 2 keep a prefix");
+  HIPEIG_REQUIRE(basis_mode >= 0 && basis_mode <= 4, "basis mode: 0 none, 1 keep, 2 keep a prefix, 3 / 4 the same in fp32");
   HIPEIG_REQUIRE(basis_mode == 0 || basis != nullptr, "null argument");
   if (basis) *basis = nullptr;
   HIPEIG_REQUIRE(basis_mode == 0 || basis_bytes >= 0, "negative byte budget");
@@ -607,12 +670,13 @@ extern "C" int hipeig_lanczos_block_scalars(hipeig_ctx* c, hipeig_csr* A, double
   if (out_stats) memset(out_stats, 0, (size_t)(1 + k) * sizeof(double));
   if (A->nrows == 0) return 0;
   hipeig_lanczos_basis** keep = basis_mode ? basis : nullptr;
-  const int prefix = basis_mode == 2;
+  const int prefix = basis_mode == 2 || basis_mode == 4;
+  const int elem = basis_mode >= 3 ? 4 : 8;
   if (lf_width(k) == 4)
     return lf_scalars_impl<4>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                              out_stats, basis_bytes, keep, prefix);
+                              out_stats, basis_bytes, keep, prefix, elem);
   return lf_scalars_impl<8>(c, A, sign, k, b, nshift, zr, zi, rtol, atol, maxiter, alphas, betas, iterations, estimates, info,
-                            out_stats, basis_bytes, keep, prefix);
+                            out_stats, basis_bytes, keep, prefix, elem);
 }
 
 // Table records of the product steps `first` .. m[j] - 1 of every column, record i at t0 + (i - first) * LF_TAB.
@@ -747,6 +811,76 @@ lf_basis_combine_kernel(int64_t n2, int mmax, const double* __restrict__ tab, co
   }
 }
 
+// The same stream over fp32 slots.  An element goes through the operations above in the same ascending order -
+// v = mul_rn(1/beta_i, (double)r32), q = fma(G, v, q), fp64 accumulators, contraction off - so the result differs from the
+// fp64 basis's only by the rounding of the stored elements: ||q32 - q64|| <= 2^-24 sum_i |g_i| ||v_i||.  A thread owns
+// CW = 4 adjacent columns of a row, which keeps the loads at 16 bytes per lane (a whole row at K = 4, half a row at
+// K = 8), with 4 NC accumulators.  (The pair mapping above with 8-byte loads was measured beside it and dropped:
+// DESIGN.md 3.6.)
+typedef float lf_floatv4 __attribute__((ext_vector_type(4)));
+
+template <int K, int NC>
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+lf_basis_combine32_kernel(int64_t nt, int mmax, const double* __restrict__ tab, const double* const* __restrict__ slots,
+                          const int* __restrict__ m, double* __restrict__ Q, int64_t nb) {
+#pragma clang fp contract(off)
+  constexpr int CW = 4;
+  typedef lf_floatv4 vec_t;
+  typedef const __attribute__((address_space(1))) vec_t* global_vec;
+  constexpr int TW = LF_BC_TAB(K, NC);
+  __shared__ double sh_tab[LF_BC_STEPS * TW];
+  __shared__ const double* sh_slot[LF_BC_STEPS];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;           // multiple of K/CW: the columns are fixed per thread
+  const int j0 = (int)(threadIdx.x % (K / CW)) * CW;                // blockDim.x is one too
+  int mj[CW];
+#pragma unroll
+  for (int x = 0; x < CW; ++x) mj[x] = m[j0 + x];
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < nt; base += stride) {   // uniform per workgroup (barriers inside)
+    const int64_t t = base + threadIdx.x;
+    const bool on = t < nt;
+    double a[CW][NC];
+#pragma unroll
+    for (int x = 0; x < CW; ++x)
+#pragma unroll
+      for (int cc = 0; cc < NC; ++cc) a[x][cc] = 0.0;
+    for (int i0 = 0; i0 < mmax; i0 += LF_BC_STEPS) {
+      const int ns = (mmax - i0 < LF_BC_STEPS) ? mmax - i0 : LF_BC_STEPS;
+      __syncthreads();
+      for (int x = threadIdx.x; x < ns * TW; x += blockDim.x) sh_tab[x] = tab[(int64_t)i0 * TW + x];
+      if ((int)threadIdx.x < ns) sh_slot[threadIdx.x] = slots[i0 + threadIdx.x];
+      __syncthreads();
+      if (!on) continue;
+      auto term = [&](int ii, const vec_t rv) {
+        const double* tb = sh_tab + ii * TW;
+#pragma unroll
+        for (int x = 0; x < CW; ++x) {
+          const double v = mul_rn(tb[j0 + x], (double)rv[x]);
+          if (i0 + ii < mj[x]) {
+#pragma unroll
+            for (int cc = 0; cc < NC; ++cc) a[x][cc] = fma(tb[K + (j0 + x) * NC + cc], v, a[x][cc]);
+          }
+        }
+      };
+      int ii = 0;
+      for (; ii + LF_BC_UNROLL <= ns; ii += LF_BC_UNROLL) {
+        vec_t rv[LF_BC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < LF_BC_UNROLL; ++u) rv[u] = ((global_vec)sh_slot[ii + u])[t];
+#pragma unroll
+        for (int u = 0; u < LF_BC_UNROLL; ++u) term(ii + u, rv[u]);
+      }
+      for (; ii < ns; ++ii) term(ii, ((global_vec)sh_slot[ii])[t]);
+    }
+    if (on) {
+#pragma unroll
+      for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int x = 0; x < CW; x += 2)
+          reinterpret_cast<double2*>(Q + (int64_t)cc * nb)[t * (CW / 2) + x / 2] = make_double2(a[x][cc], a[x + 1][cc]);
+    }
+  }
+}
+
 // ---- pass 2, host side -------------------------------------------------------------------------------------------------
 // One path with a plan (prefix_split in lanczos_filter.py states it): the terms i < stream come from the basis's slots in
 // one stream (columns masked by min(m_j, stream)) that leaves Q packed in the workspace; the recurrence takes over at step
@@ -754,6 +888,7 @@ lf_basis_combine_kernel(int64_t n2, int mmax, const double* __restrict__ tab, co
 //   no basis                stream = 0        r_0 = packed b, r_{-1} = zeros                          mmax - 1 products
 //   basis holds p >= mmax   stream = mmax     -                                                       none
 //   basis holds p <  mmax   stream = p - 1    r_{p-1}, r_{p-2} copied from their slots (zeros, p = 1)  mmax - p products
+//                                             (an fp32 basis: from its fp64 hand-over vectors)
 // The basis is never written: it serves any number of calls.  Every element meets the mul_rn / fma sequence of the
 // product steps in ascending i (the stream's accumulators start from 0, as Q does without a stream), so with the
 // row-owner sweep the three situations agree bit for bit.
@@ -829,22 +964,30 @@ static int lf_pass2_impl(hipeig_ctx* c, hipeig_csr* A, const hipeig_lanczos_basi
   free(h_tab);
   HIPEIG_CHECK(e);
   const int* d_ms = reinterpret_cast<const int*>(d_tab + P.o_m);
-  if (P.stream > 0)
+  const bool narrow = B && B->elem_bytes == 4;
+  const double* const* d_slots = reinterpret_cast<const double* const*>(d_tab + P.o_slots);
+  if (P.stream > 0 && !narrow)
     hipLaunchKernelGGL((lf_basis_combine_kernel<K, NC>), dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream,
-                       n * (K / 2), P.stream, (const double*)d_tab, reinterpret_cast<const double* const*>(d_tab + P.o_slots),
-                       d_ms, Q, nb);
+                       n * (K / 2), P.stream, (const double*)d_tab, d_slots, d_ms, Q, nb);
+  else if (P.stream > 0)
+    hipLaunchKernelGGL((lf_basis_combine32_kernel<K, NC>), dim3(grid_stream(n * K / 2)), dim3(HIPEIG_BLOCK), 0, c->stream,
+                       n * (K / 4), P.stream, (const double*)d_tab, d_slots, d_ms, Q, nb);
   else                                                        // no stream: the recurrence starts at step 0, r_{-1} = Q = 0
     HIPEIG_CHECK(hipMemsetAsync(Vb[1], 0, (size_t)nb * (1 + NC) * sizeof(double), c->stream));
   HIPEIG_CHECK(hipGetLastError());
   if (P.recurs()) {
     const int first = P.stream;
+    if (narrow) {
+      HIPEIG_REQUIRE(B->hand[0] && B->hand[1], "an fp32 prefix without its hand-over vectors");
+    }
     if (B)
-      HIPEIG_CHECK(hipMemcpyAsync(Vb[first & 1], lf_slot(B, first), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPEIG_CHECK(hipMemcpyAsync(Vb[first & 1], narrow ? B->hand[0] : lf_slot(B, first), (size_t)nb * sizeof(double),
+                                  hipMemcpyDeviceToDevice, c->stream));
     else if (hipeig_block_pack(c, K, n, k, b, Vb[0]))
       return 1;
     if (first)
-      HIPEIG_CHECK(hipMemcpyAsync(Vb[(first + 1) & 1], lf_slot(B, first - 1), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice,
-                                  c->stream));
+      HIPEIG_CHECK(hipMemcpyAsync(Vb[(first + 1) & 1], narrow ? B->hand[1] : lf_slot(B, first - 1), (size_t)nb * sizeof(double),
+                                  hipMemcpyDeviceToDevice, c->stream));
     if (lf_enqueue_products<K, NC>(c, A, d_tab + P.o_prod, d_ms + K, first, P.mmax, Vb, Q, nb)) return 1;
   }
   if (lf_unpack_combinations<K, NC>(c, n, k, Q, nb, q)) return 1;
@@ -896,12 +1039,18 @@ extern "C" int hipeig_lanczos_basis_info(hipeig_ctx* c, const hipeig_lanczos_bas
   int top = 0;
   for (int j = 0; j < B->k; ++j) top = B->steps[j] > top ? B->steps[j] : top;
   info[0] = top;
-  info[1] = (int64_t)B->nseg * (int64_t)B->seg_bytes;
+  info[1] = (int64_t)B->nseg * (int64_t)B->seg_bytes + (B->hand[0] ? 2 * B->nb * (int64_t)sizeof(double) : 0);
   info[2] = B->K;
   info[3] = B->n;
   info[4] = B->k;
   info[6] = B->nseg;
   info[7] = B->seg_slots;
+  return 0;
+}
+
+extern "C" int hipeig_lanczos_basis_element_bytes(hipeig_ctx* c, const hipeig_lanczos_basis* B, int* out) {
+  HIPEIG_REQUIRE(out != nullptr, "null argument");
+  *out = B ? B->elem_bytes : 0;
   return 0;
 }
 

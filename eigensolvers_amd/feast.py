@@ -251,11 +251,12 @@ def _lanczos_filter_sums(cls, A, Y, pairs, nodes, radius, contourEllipseFactor, 
     the recurrence takes a real z as well.  (Vectors that hold different points - ``contourDeal="balanced"`` - take one
     call per distinct set.)  Returns (Q, record): the backend's runs (groups of right-hand sides that advanced in lock
     step), the block products of each pass per run, whether the run's Lanczos basis was ``"kept"``, held as a ``"prefix"``
-    or ``"recomputed"`` for pass 2, the vectors it held (``"basis_vectors"``), and the steps per (point, vector)."""
+    or ``"recomputed"`` for pass 2, the vectors it held (``"basis_vectors"``) and in which precision
+    (``"basis_precision"``), and the steps per (point, vector)."""
     nsub = len(Y)
     Q = [None] * nsub
-    record = {"runs": 0, "products_pass1": [], "products_pass2": [], "basis": [], "basis_vectors": [], "pairs": [],
-              "steps": []}
+    record = {"runs": 0, "products_pass1": [], "products_pass2": [], "basis": [], "basis_vectors": [],
+              "basis_precision": [], "pairs": [], "steps": []}
     by_points = {}
     for im0 in range(nsub):
         points = tuple(sorted(k for k, i in pairs if i == im0))
@@ -282,6 +283,7 @@ def _lanczos_filter_sums(cls, A, Y, pairs, nodes, radius, contourEllipseFactor, 
                 record["products_pass2"].append(stats.get("products_pass2"))
                 record["basis"].append(stats.get("basis"))
                 record["basis_vectors"].append(stats.get("basis_vectors"))
+                record["basis_precision"].append(stats.get("basis_precision"))
             its = stats.get("iterations") or [None] * len(points)
             for k, n_it in zip(points, its):
                 record["pairs"].append([k, im0])

@@ -506,7 +506,7 @@ class HipVector(AbstractVector):
         lsa.setdefault("linear_atol", 1e-4)
         self.options = {"linearSystemArgs": lsa}
         for extra in ("orthogonalization", "blockSolve", "reduction", "contourPoolWidth", "lanczosBasis", "lanczosBasisBytes",
-                      "lanczosBasisPrefix"):
+                      "lanczosBasisPrefix", "lanczosBasisPrecision"):
             if extra in given:
                 self.options[extra] = given[extra]
         self.last_solve_stats = None
@@ -739,14 +739,18 @@ class HipVector(AbstractVector):
         ``"lanczos_filter"``.  ``B[0].options["lanczosBasis"]`` (``"recompute"``, the default, or ``"keep"``) and
         ``["lanczosBasisBytes"]`` choose whether pass 1 keeps its vectors for pass 2 and the byte budget of that;
         ``["lanczosBasisPrefix"]: True`` (only with ``"keep"``, ``ValueError`` otherwise) lets a basis that outgrows the
-        budget keep the vectors that fit."""
+        budget keep the vectors that fit; ``["lanczosBasisPrecision"]: "fp32"`` (only with ``"keep"`` too) stores the basis
+        in fp32."""
         from .lanczos_filter import lanczos_filter
         B = list(B)
         o = B[0].options if B else {}
         if o.get("lanczosBasisPrefix") and o.get("lanczosBasis", "recompute") != "keep":
             raise ValueError('"lanczosBasisPrefix" keeps a prefix of a kept basis: it needs "lanczosBasis": "keep"')
+        if o.get("lanczosBasisPrecision", "fp64") == "fp32" and o.get("lanczosBasis", "recompute") != "keep":
+            raise ValueError('"lanczosBasisPrecision": "fp32" stores a kept basis in fp32: it needs "lanczosBasis": "keep"')
         return lanczos_filter(H, B, shifts, weights, reverseGF=reverseGF, basis=o.get("lanczosBasis", "recompute"),
-                              basisBytes=o.get("lanczosBasisBytes"), prefix=bool(o.get("lanczosBasisPrefix", False)))
+                              basisBytes=o.get("lanczosBasisBytes"), prefix=bool(o.get("lanczosBasisPrefix", False)),
+                              precision=o.get("lanczosBasisPrecision", "fp64"))
 
     BLOCK_SOLVE_MIN = 3      # fewer right-hand sides are solved one by one (measured at N = 1e6: 2 columns 0.97x, 3: 1.6x, 4: 1.95x, 8: 2.8x)
 

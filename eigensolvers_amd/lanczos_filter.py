@@ -15,7 +15,9 @@ With ``keepBasis`` / ``basis="keep"`` pass 1 keeps its vectors in device memory 
 basis, is one stream over them: no second set of products, any number of combinations.  With ``keepPrefix`` /
 ``prefix=True`` on top (``basis_mode`` 2), a basis that outgrows its byte budget keeps its first ``p`` vectors: the stream
 serves the terms ``i < p - 1`` and the recurrence restarts from the two last kept vectors, ``m - p`` products instead of
-``m - 1``.  ``prefix_split`` is the plan of all three.
+``m - 1``.  ``prefix_split`` is the plan of all three.  ``basisPrecision`` / ``precision="fp32"`` (``basis_mode`` 3 / 4)
+stores that basis in fp32, twice the vectors per byte: pass 1, its scalars and the coefficients stay fp64 bit for bit, only
+the copy pass 2 streams over is rounded (``lanczos_combine_stored_host`` states it and its error bound).
 
 Both passes are an operator product plus a row epilogue, so up to 8 right-hand sides advance in lock step on the
 interleaved block products of ``csrc/spmm_device.h``.  The ``*_host`` functions are the NumPy statement - the
@@ -33,11 +35,13 @@ import numpy as np
 __all__ = ["lanczos_scalars_host", "minres_coefficients", "filter_coefficients", "lanczos_combine_host",
            "lanczos_filter_host", "lanczos_run", "lanczos_filter", "LanczosRun", "LanczosScalars", "MAX_COLUMNS_PER_CALL",
            "MAX_SHIFTS_PER_RUN", "basis_budget", "split_combinations", "BASIS_MODES", "lanczos_vectors_host",
-           "lanczos_combine_prefix_host", "prefix_split"]
+           "lanczos_combine_prefix_host", "prefix_split", "BASIS_PRECISIONS", "lanczos_combine_stored_host",
+           "basis_slot_bytes"]
 
 MAX_COLUMNS_PER_CALL = 8
 MAX_SHIFTS_PER_RUN = 32
 BASIS_MODES = ("recompute", "keep")
+BASIS_PRECISIONS = ("fp64", "fp32")      # storage of a kept basis; the recurrence and its scalars are fp64 either way
 BASIS_SAFETY = 0.9                       # share of the memory in sight a kept basis may take, as the contour pool's
 BASIS_COMBINE_WIDTHS = (8, 4, 2, 1)      # combinations per column one hipeig_lanczos_combine call takes from a basis
 
@@ -52,6 +56,17 @@ def basis_budget(hbm_free, reusable, override=None, held=0):
             raise ValueError("basisBytes must not be negative")
         return max(0, int(override) - int(held))
     return max(0, int(BASIS_SAFETY * (int(hbm_free) + int(reusable))))
+
+
+def basis_slot_bytes(n, k, precision="fp64"):
+    """Bytes of one slot - one Lanczos vector of a k-column group - of a kept basis: the interleaved block of width 4
+    (k <= 4) or 8, padded to 32 elements, of 8-byte or (``"fp32"``) 4-byte elements."""
+    if precision not in BASIS_PRECISIONS:
+        raise ValueError(f"precision must be one of {BASIS_PRECISIONS}, not {precision!r}")
+    if not 1 <= int(k) <= MAX_COLUMNS_PER_CALL:
+        raise ValueError(f"1 to {MAX_COLUMNS_PER_CALL} columns per group")
+    width = 4 if int(k) <= 4 else 8
+    return (int(n) * width + 31) // 32 * 32 * (4 if precision == "fp32" else 8)
 
 
 def split_combinations(nc):
@@ -88,6 +103,15 @@ def _checked_prefix(prefix, keeps, what):
     if prefix and not keeps:
         raise ValueError(f"{what}: keeping a prefix of the basis needs the basis to be kept")
     return bool(prefix)
+
+
+def _checked_precision(value, keeps, what):
+    """``value`` is one of ``BASIS_PRECISIONS``, and ``"fp32"`` only makes sense for a kept basis."""
+    if value not in BASIS_PRECISIONS:
+        raise ValueError(f"{what} must be one of {BASIS_PRECISIONS}, not {value!r}")
+    if value == "fp32" and not keeps:
+        raise ValueError(f"{what}: storing the basis in fp32 needs the basis to be kept")
+    return value
 
 
 def _checked_basis_mode(value, what):
@@ -331,6 +355,55 @@ def lanczos_combine_prefix_host(matvec, V, alphas, betas, G):
     return q
 
 
+def lanczos_combine_stored_host(matvec, b, alphas, betas, G, p, dtype=np.float64):
+    """Pass 2 of one column from a basis stored in ``dtype``: the NumPy statement of ``basis_mode`` 3 / 4.  Returns
+    ``[NC, n]`` (``G``: ``[m]`` or ``[m, NC]``).
+
+    Pass 1's recurrence (the expressions of ``lanczos_combine_host``, fp64) leaves the un-normalised ``r_i = beta_i v_i``
+    of the first ``p`` vectors (``r_0 = b``; ``1 <= p <= len(alphas)``) in an array of ``dtype``.  The terms
+    ``prefix_split(m, p)`` assigns to the stream are formed from it as ``v = r_i / beta_i`` - the stored element widened to
+    fp64, then this twin's own normalisation (the device multiplies by the ``1 / beta_i`` its pass 1 used) - and added in
+    ascending i in fp64; the tail runs the recurrence in fp64 from the exact ``v_{p-2}``, ``v_{p-1}``, never from the
+    stored copies.  With ``dtype=np.float64`` nothing is rounded and the result is ``lanczos_combine_prefix_host``'s bit
+    for bit.
+
+    With ``dtype=np.float32`` a stored element carries a relative error of at most 2^-24, so per combination c
+    ``||q32 - q64||_2 <= 2^-24 sum_{i in stream} |G[i, c]| ||v_i||``, and ``||v_i|| = 1``.  Precondition: the vectors are
+    stored un-normalised, so the bound holds while their elements stay in fp32's normal range (about 1e-38 .. 3e38 in
+    magnitude; smaller ones lose relative accuracy, larger ones overflow).  ``||r_i|| = beta_i`` is of the size of
+    ``||H||`` for i >= 1 and ``||b||`` for i = 0; FEAST's subspace vectors are normalised, so there the precondition is
+    one on the operator's scale alone."""
+    b = np.asarray(b, dtype=np.float64)
+    a, bt = np.asarray(alphas, dtype=np.float64), np.asarray(betas, dtype=np.float64)
+    g = np.asarray(G, dtype=np.float64)
+    g = g[:, None] if g.ndim == 1 else g
+    m, nc = g.shape
+    p = int(p)
+    if not 1 <= p <= len(a):
+        raise ValueError("1 to len(alphas) vectors")
+    R = np.zeros((p, b.size), dtype=dtype)
+    R[0] = b
+    v_old, v = np.zeros(b.size), b / bt[0]
+    for i in range(p - 1):
+        w = matvec(v) - (bt[i] if i else 0.0) * v_old
+        w = w - a[i] * v
+        R[i + 1] = w                                      # rounded to dtype here, to nearest even
+        v_old, v = v, w / bt[i + 1]
+    q = np.zeros((nc, b.size))
+    stream, products = prefix_split(m, p)
+    for i in range(stream):
+        q += g[i][:, None] * (R[i].astype(np.float64) / bt[i])[None, :]
+    if m <= p:
+        return q
+    for i in range(p - 1, m):                             # v_old, v are the exact v_{p-2}, v_{p-1}
+        q += g[i][:, None] * v[None, :]
+        if i + 1 < m:
+            w = matvec(v) - (bt[i] if i else 0.0) * v_old
+            w = w - a[i] * v
+            v_old, v = v, w / bt[i + 1]
+    return q
+
+
 def lanczos_filter_host(matvec, B, shifts, weights, rtol, atol, maxiter, sign=1.0):
     """``(q[K, n], scalars)`` with ``q_r = sum_j Re(weights[j] x_{j,r})``, ``x_{j,r}`` the MINRES iterate of
     ``sign*(z_j I - H) x = B[r]`` at its own stop step; ``scalars`` is pass 1's result.  A shift still live at the step
@@ -352,10 +425,12 @@ class LanczosRun:
     ``basis_kept[g]`` tells whether group g's Lanczos vectors stayed in device memory, ``basis_bytes`` what they hold and
     ``release()`` gives them back; ``combine`` then streams over them instead of repeating the products.  With
     ``keepPrefix=True`` a group may hold only its first ``basis_vectors[g]`` vectors (``basis_kept[g]`` is then False);
-    ``combine`` streams over those and repeats the products of the rest."""
+    ``combine`` streams over those and repeats the products of the rest.  ``basis_precision`` is the storage asked for
+    (``"fp64"`` or ``"fp32"``): ``combine`` is the same call either way."""
 
-    def __init__(self, H, B, shifts, sign):
+    def __init__(self, H, B, shifts, sign, basis_precision="fp64"):
         self.H, self.B, self.shifts, self.sign = H, list(B), list(shifts), sign
+        self.basis_precision = basis_precision
         self.scalars, self.info, self.groups, self.products_pass1, self.products_pass2 = [], [], [], [], []
         self._bases = []                                  # per group: the basis handle, or None
         self._finalizer = weakref.finalize(self, _release_bases, self.B[0].ctx, self._bases)
@@ -379,6 +454,17 @@ class LanczosRun:
         info = (C.c_int64 * 8)()
         _lib.call("hipeig_lanczos_basis_info", self.B[0].ctx.handle, self._bases[g], info)
         return list(info)
+
+    @property
+    def basis_element_bytes(self):
+        """Bytes of one stored element per group (8 or 4), 0 without a basis."""
+        from . import _lib
+        out = []
+        for h in self._bases:
+            nbytes = C.c_int(0)
+            _lib.call("hipeig_lanczos_basis_element_bytes", self.B[0].ctx.handle, h, C.byref(nbytes))
+            out.append(int(nbytes.value))
+        return out
 
     @property
     def basis_bytes(self):
@@ -461,7 +547,7 @@ def _default_basis_budget(ctx, basisBytes, held):
     return basis_budget(ctx.device_info()["hbm_free"], info[5])
 
 
-def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None, keepPrefix=False):
+def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None, keepPrefix=False, basisPrecision="fp64"):
     """Pass 1 on the device (``hipeig_lanczos_block_scalars``) for the real ``HipVector``s ``B`` and up to 32 ``shifts``
     (real or complex) of ``sign*(z I - H)``, ``sign = -1`` with ``reverseGF``: a ``LanczosRun``.  More than 8 columns are
     grouped into calls of 8, each in lock step on block products.  Tolerances and the step limit come from
@@ -472,10 +558,16 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None,
     device memory.  A group whose basis does not fit finishes as a plain pass 1; ``run.basis_kept`` tells.
 
     ``keepPrefix`` (with ``keepBasis``): such a group keeps the vectors that fit instead (``basis_mode`` 2, again the same
-    scalars); ``run.basis_vectors`` tells how many."""
+    scalars); ``run.basis_vectors`` tells how many.
+
+    ``basisPrecision="fp32"`` (with ``keepBasis``): the basis is stored in fp32 (``basis_mode`` 3, with ``keepPrefix`` 4) -
+    twice the vectors per byte of budget.  The recurrence and its scalars are the plain run's; pass 1 writes ``4 n K`` more
+    bytes per step, and ``combine`` differs from the fp64 basis's result by the rounding of the stored elements
+    (``lanczos_combine_stored_host`` has the bound and its precondition)."""
     from . import _lib
     from .hip_vector import _ptr_table
     keepPrefix = _checked_prefix(keepPrefix, keepBasis, "lanczos_run(keepPrefix=True)")
+    basisPrecision = _checked_precision(basisPrecision, keepBasis, "lanczos_run(basisPrecision)")
     B = _checked_inputs(H, B, "lanczos_run")
     if basisBytes is not None and int(basisBytes) < 0:
         raise ValueError("basisBytes must not be negative")
@@ -487,7 +579,8 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None,
     o = B[0].options["linearSystemArgs"]
     rtol, atol, maxiter = float(o["linear_tol"]), float(o.get("linear_atol", 0.0)), int(o["linearIter"])
     sign = -1.0 if reverseGF else 1.0
-    run = LanczosRun(H, B, zs, sign)
+    run = LanczosRun(H, B, zs, sign, basisPrecision)
+    mode = (2 if keepPrefix else 1 if keepBasis else 0) + (2 if basisPrecision == "fp32" else 0)
     S = len(zs)
     zr = (C.c_double * S)(*[z.real for z in zs])
     zi = (C.c_double * S)(*[z.imag for z in zs])
@@ -506,7 +599,7 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None,
         budget = _default_basis_budget(ctx, basisBytes, run.basis_bytes) if keepBasis else 0
         _lib.call("hipeig_lanczos_block_scalars", ctx.handle, H.handle, sign, k, bt, S, zr, zi, rtol, atol, maxiter,
                   alphas.ctypes.data_as(dp), betas.ctypes.data_as(dp), its, est, info, stats,
-                  2 if keepPrefix else 1 if keepBasis else 0, budget, C.byref(basis))
+                  mode, budget, C.byref(basis))
         run._bases.append(C.c_void_p(basis.value) if basis.value else None)
         run.groups.append((lo, hi))
         run.products_pass1.append(int(stats[0]))
@@ -519,19 +612,22 @@ def lanczos_run(H, B, shifts, reverseGF=False, keepBasis=False, basisBytes=None,
     return run
 
 
-def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", basisBytes=None, prefix=False):
+def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", basisBytes=None, prefix=False,
+                   precision="fp64"):
     """``[q_r]`` (``HipVector``) with ``q_r = sum_j Re(weights[j] x_{j,r})``, ``x_{j,r}`` the MINRES iterate of
     ``sign*(z_j I - H) x = B[r]`` at its own stop step - FEAST's filtered vectors with ``weights[j] = -0.5 w_j r phase_j`` -
     from two Lanczos passes on the device, no solution ever formed.  Every ``b.last_solve_stats`` = ``{"iterations":
     [per shift], "estimates": [|tau_j|], "products": block products of both passes of b's group, "products_pass1",
-    "products_pass2", "basis": "kept" | "prefix" | "recomputed", "basis_vectors": vectors of the group held for pass 2}``.  A shift still live at the step limit raises ``UserWarning`` as
+    "products_pass2", "basis": "kept" | "prefix" | "recomputed", "basis_vectors": vectors of the group held for pass 2, "basis_precision": "fp64" | "fp32"}``.  A shift still live at the step limit raises ``UserWarning`` as
     every other solver does.
 
     ``basis="keep"``: group by group - pass 1 with its vectors kept, coefficients, one stream over the vectors, release - so
     at most one group's basis is alive at a time and every group has the whole budget (``basisBytes``, default
     ``basis_budget``).  A group whose basis does not fit is served by the product pass and reports ``"recomputed"`` - or,
-    with ``prefix=True``, keeps the vectors that fit, repeats only the products behind them and reports ``"prefix"``."""
+    with ``prefix=True``, keeps the vectors that fit, repeats only the products behind them and reports ``"prefix"``.
+    ``precision="fp32"`` (with ``basis="keep"``) stores the basis in fp32, see ``lanczos_run``."""
     prefix = _checked_prefix(prefix, basis == "keep", "lanczos_filter(prefix=True)")
+    precision = _checked_precision(precision, basis == "keep", "lanczos_filter(precision)")
     B = _checked_inputs(H, B, "lanczos_filter")
     _checked_basis_mode(basis, "basis")
     if len(np.asarray(weights).reshape(-1)) != len(np.asarray(shifts).reshape(-1)):
@@ -543,7 +639,7 @@ def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", ba
     q, converged = [], True
     for first, (lo, hi) in enumerate(spans):
         run = lanczos_run(H, B[lo:hi], shifts, reverseGF=reverseGF, keepBasis=basis == "keep", basisBytes=basisBytes,
-                          keepPrefix=prefix)
+                          keepPrefix=prefix, basisPrecision=precision)
         try:
             G = filter_coefficients(run.scalars, run.shifts, weights, run.sign)
             part = run.combine(G) if run.converged else None
@@ -560,7 +656,7 @@ def lanczos_filter(H, B, shifts, weights, reverseGF=False, basis="recompute", ba
                                       "estimates": [float(e) for e in run.scalars[r].estimates],
                                       "products": p1 + p2, "products_pass1": p1, "products_pass2": p2, "group": first + g,
                                       "basis": "kept" if kept[g] else "prefix" if held[g] else "recomputed",
-                                      "basis_vectors": held[g]}
+                                      "basis_vectors": held[g], "basis_precision": precision}
                 if part is not None:
                     part[r].last_solve_stats = b.last_solve_stats
         if part is not None:

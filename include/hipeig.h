@@ -349,7 +349,14 @@ int hipeig_minres_shifts(hipeig_ctx* ctx, hipeig_csr* A, double sign, int nshift
  * the ring; steps p - 1 and p read their operands from the slots, so kernels, operands and scalars are still mode 0's.
  * The basis then holds min(steps of column j, p) vectors per column.  A run that stops before p ends as a whole basis;
  * *basis is NULL only when not even the first segment fits.  The workspace of the pass 2 that follows (nc <= 2) is reserved
- * before the first segment.                                                                                            */
+ * before the first segment.
+ * basis_mode 3 / 4 (basisPrecision="fp32"): modes 1 / 2 with the basis stored in fp32, twice the vectors per byte.  The
+ * recurrence runs in the fp64 ring of three exactly as mode 0 (the same scalars), and the kernel that finishes step k's
+ * vector also leaves it, rounded to nearest even, in slot k + 1 (slot 0: b): 4 n K more bytes written per step.  A slot is
+ * n K floats (padded to 32), so a segment is half the bytes.  Mode 3: a refused segment frees the basis, *basis is NULL.
+ * Mode 4: the slots held stay, and r_{p-1}, r_{p-2} are copied in fp64 to two hand-over vectors the basis owns, from which
+ * pass 2's recurrence restarts (rounded start vectors would not repeat pass 1's arithmetic).  basis_bytes is the budget of
+ * the segments; the hand-over vectors (16 bytes per padded element of a slot) come on top and are freed, not pooled.   */
 typedef struct hipeig_lanczos_basis hipeig_lanczos_basis;
 int hipeig_lanczos_block_scalars(hipeig_ctx* ctx, hipeig_csr* A, double sign, int k, const double* const* b,
                                  int nshift, const double* zr, const double* zi, double rtol, double atol,
@@ -366,6 +373,9 @@ int hipeig_lanczos_block_scalars(hipeig_ctx* ctx, hipeig_csr* A, double sign, in
  *     no product, any number of calls per basis; k must be the basis's column count and A the operator it was kept for;
  *   a basis that holds p < mmax: the stream takes the terms i < p - 1, r_{p-2} and r_{p-1} are copied out of their slots
  *     (the basis is never written) and the recurrence runs from step p - 1: mmax - p block products.
+ * An fp32 basis (basis_mode 3 / 4) is taken the same way: the stream widens every stored element to fp64 and then makes
+ * the same operations in the same order, so each q differs from the fp64 basis's by at most 2^-24 sum_i |G[j][i]| ||v_i||
+ * over the stream's terms; the recurrence behind a prefix starts from the fp64 hand-over vectors.
  * out_stats[0] (may be NULL) = block products made.  Every element meets the same operations in the same order in the
  * three situations: with the row-owner sweep the results are equal bit for bit.                                        */
 int hipeig_lanczos_combine(hipeig_ctx* ctx, hipeig_csr* A, const hipeig_lanczos_basis* basis, int k,
@@ -373,9 +383,11 @@ int hipeig_lanczos_combine(hipeig_ctx* ctx, hipeig_csr* A, const hipeig_lanczos_
                            const double* const* betas, int nc, const double* const* G, double* const* q,
                            double* out_stats);
 /* What a kept basis holds (lanczos_filter.py, LanczosRun.basis_bytes and default_basis_budget): info[0] vectors kept (the
- * largest column's; behind a prefix at most its p), [1] bytes of its segments, [2] interleave width K, [3] rows, [4] columns, [5] bytes of released
+ * largest column's; behind a prefix at most its p), [1] bytes held: its segments, and the two fp64 hand-over vectors of an fp32 prefix, [2] interleave width K, [3] rows, [4] columns, [5] bytes of released
  * segments the context would hand out again, [6] segments, [7] slots per segment.  basis may be NULL: only [5] is set. */
 int hipeig_lanczos_basis_info(hipeig_ctx* ctx, const hipeig_lanczos_basis* basis, int64_t info[8]);
+/* Bytes of one stored element of a kept basis: *out = 8, or 4 for basis_mode 3 / 4; 0 when basis is NULL. */
+int hipeig_lanczos_basis_element_bytes(hipeig_ctx* ctx, const hipeig_lanczos_basis* basis, int* out);
 /* Give a kept basis's segments back to the context for reuse (lanczos_filter.py, LanczosRun.release); basis may be NULL.
  * The context frees them when an allocation fails and when it is destroyed.                                           */
 int hipeig_lanczos_basis_release(hipeig_ctx* ctx, hipeig_lanczos_basis* basis);

@@ -7,7 +7,8 @@ subspace vectors, 16 Legendre nodes = 8 contour points, window [-0.21, 0.21], in
 on block products, no per-shift vector) and with the same plus ``"lanczosBasis": "keep"`` (mode ``basis``: pass 1 keeps its
 vectors in device memory and pass 2 is one stream over them) and with that plus ``"lanczosBasisPrefix": True`` (mode
 ``prefix``: a basis that outgrows the byte budget keeps the vectors that fit, and pass 2 repeats only the products behind
-them), the modes alternating.  One JSON line per run as soon as it
+them) and with ``basis`` / ``prefix`` plus ``"lanczosBasisPrecision": "fp32"`` (modes ``basis32`` / ``prefix32``: the basis
+stored in fp32, twice the vectors per byte), the modes alternating.  One JSON line per run as soon as it
 is measured; the first line describes the device.
 
 Then the per-phase split of one shared solve (``--phases``, default on): the whole 8-shift solve of the first subspace
@@ -18,9 +19,10 @@ one 8-column run with pass 1, the host's coefficients and pass 2 timed apart, pa
 (HIPEIG_LF_PROBE = 1 sweep / 2 second kernel / 3 scalar kernel), and the block sweep's time per column.  For the ``basis``
 mode: one 8-column run with the keeping pass 1 and the combination from the kept basis timed apart - the combination's ms
 per group and its TB/s against the byte model 8 n K m + 8 n K NC (m slots read, NC outputs written), for NC = 1, 2 and 8 -
-and the bytes the basis holds.
+and the bytes the basis holds.  For the ``basis32`` mode the same split on the fp32 basis (``basis32_phases``), byte model
+4 n K m + 8 n K NC.
 
-    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted,filter,basis,prefix] >> profiles/NN_shifted_feast.jsonl
+    python tools/shifted_feast_bench.py [--n 1000000 --reps 3 --modes gcrotmk,shifted,filter,basis,prefix,basis32,prefix32] >> profiles/NN_shifted_feast.jsonl
 
 ``--cpu``: instead, the NumPy twins on the host generator's operator (small N): products per shift of the shared-Lanczos
 solver, and the two-pass filter's products and its difference from the former's sum; no timing claims;
@@ -110,10 +112,13 @@ def main():
            "filter": {"linearSolver": "lanczos_filter", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7},
            "basis": {"linearSolver": "lanczos_filter", "linearIter": 4000, "linear_tol": 1e-5, "linear_atol": 1e-7}}
     lsa["prefix"] = dict(lsa["basis"])
+    lsa["basis32"], lsa["prefix32"] = dict(lsa["basis"]), dict(lsa["basis"])
     extra = {"basis": {"lanczosBasis": "keep"}, "prefix": {"lanczosBasis": "keep", "lanczosBasisPrefix": True}}
+    extra["basis32"] = dict(extra["basis"], lanczosBasisPrecision="fp32")
+    extra["prefix32"] = dict(extra["prefix"], lanczosBasisPrecision="fp32")
     if a.basis_bytes is not None:
-        extra["basis"]["lanczosBasisBytes"] = a.basis_bytes
-        extra["prefix"]["lanczosBasisBytes"] = a.basis_bytes
+        for mode in extra:
+            extra[mode]["lanczosBasisBytes"] = a.basis_bytes
     Y0 = la.qr(rng.standard_normal((N, m0)), mode="economic")[0]
     ctx = ea.HipContext.default()
     print(json.dumps({"device": ctx.device_info()["name"], "N": N, "m0": m0, "contour_points": a.nc // 2, "reps": a.reps,
@@ -154,11 +159,11 @@ def main():
                             "iterations_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk)),
                                                               int(max(i for (k, v), i in zip(rec["pairs"], rec["iterations"]) if k == kk))]
                                                              for kk in range(a.nc // 2)]})
-            elif mode in ("filter", "basis", "prefix"):
+            elif mode in ("filter", "basis", "prefix", "basis32", "prefix32"):
                 rec = st["lanczosFilter"][0]
                 row.update({"runs": rec["runs"], "block_products_pass1": rec["products_pass1"],
                             "block_products_pass2": rec["products_pass2"], "basis": rec["basis"],
-                            "basis_vectors": rec.get("basis_vectors"),
+                            "basis_vectors": rec.get("basis_vectors"), "basis_precision": rec.get("basis_precision"),
                             "steps_per_point_min_max": [[int(min(i for (k, v), i in zip(rec["pairs"], rec["steps"]) if k == kk)),
                                                          int(max(i for (k, v), i in zip(rec["pairs"], rec["steps"]) if k == kk))]
                                                         for kk in range(a.nc // 2)]})
@@ -263,7 +268,9 @@ def main():
                           "sweep_ms_per_column": round(phase["sweep"] / K, 5), "hipeig_spmv_ms": round(spmv_ms, 5),
                           "second_kernel_TBps": round(24 * N * K / (phase["second_kernel"] * 1e-3) / 1e12, 3)}), flush=True)
 
-    if a.phases and "basis" in modes:
+    for precision, key in (("fp64", "basis"), ("fp32", "basis32")):
+        if not (a.phases and key in modes):
+            continue
         import importlib
         import math
         from eigensolvers_amd import feast as pf
@@ -275,9 +282,9 @@ def main():
         K = min(8, m0)
         B = [ea.HipVector(Y0[:, i].copy(), {"linearSystemArgs": dict(lsa["basis"])}, ctx=ctx) for i in range(K)]
         os.environ.pop("HIPEIG_LF_PROBE", None)
-        ea.lanczos_filter(H, B, zs, ws, basis="keep", basisBytes=a.basis_bytes)   # warm (workspace, operator copy, reusable segments)
+        ea.lanczos_filter(H, B, zs, ws, basis="keep", basisBytes=a.basis_bytes, precision=precision)   # warm (workspace, operator copy, reusable segments)
         ctx.timer_start()
-        run = ea.lanczos_run(H, B, zs, keepBasis=True, basisBytes=a.basis_bytes)
+        run = ea.lanczos_run(H, B, zs, keepBasis=True, basisBytes=a.basis_bytes, basisPrecision=precision)
         pass1_ms = ctx.timer_stop()
         kept, held = run.basis_kept, run.basis_bytes
         t0 = time.perf_counter()
@@ -285,7 +292,9 @@ def main():
         host_ms = (time.perf_counter() - t0) * 1e3
         width = 4 if K <= 4 else 8
         m = max(len(g) for g in G)
-        row = {"label": a.label, "N": N, "mode": "basis_phases", "columns": K, "shifts": len(zs),
+        elem = 4.0 if precision == "fp32" else 8.0
+        row = {"label": a.label, "N": N, "mode": key + "_phases", "columns": K, "shifts": len(zs),
+               "basis_precision": precision,
                "block_variant": H.block_info()["variant"], "basis_kept": kept, "basis_bytes": held,
                "block_products_pass1": run.products_pass1[0], "pass1_keep_ms": round(pass1_ms, 3),
                "pass1_keep_ms_per_step": round(pass1_ms / run.products_pass1[0], 5),
@@ -300,7 +309,7 @@ def main():
                 ctx.timer_start()
                 run.combine(Gn)
                 times.append(ctx.timer_stop())
-            model = 8.0 * N * width * m + 8.0 * N * width * nc
+            model = elem * N * width * m + 8.0 * N * width * nc
             best, med = min(times), sorted(times)[len(times) // 2]
             row.update({f"combine_nc{nc}_ms_per_group": [round(t, 3) for t in times],
                         f"combine_nc{nc}_ms_median": round(med, 3), f"combine_nc{nc}_model_bytes": int(model),
