@@ -102,6 +102,9 @@ SIGNATURES = {
     "hipeig_spmm_shift_pairs_z": [_P, _P, C.c_int, _DP, _DP, _D, _PP, _PP, _PP, _PP],
     "hipeig_minres": [_P, _P, _D, _D, _P, _P, _D, C.c_int, _IP, _DP],
     "hipeig_minres_x0": [_P, _P, _D, _D, _P, _P, _P, _D, C.c_int, _IP, _DP],
+    "hipeig_csr_diagonal": [_P, _P, _P],
+    "hipeig_jacobi_inverse": [_P, _I64, _P, _D, _D, _P],
+    "hipeig_minres_jacobi": [_P, _P, _D, _D, _P, _P, _P, _D, C.c_int, _IP, _DP],
     "hipeig_dense_solve_small": [_P, _P, _D, _D, _D, _P, _P, _P, _P, _IP],
     "hipeig_minres_block": [_P, _P, _D, _D, C.c_int, _PP, _PP, _D, C.c_int, _IP, _DP],
     "hipeig_minres_shifts": [_P, _P, _D, C.c_int, _DP, _DP, _P, _PP, _PP, _D, _D, C.c_int, _IP, _DP],

@@ -200,6 +200,9 @@ struct hipeig_ctx {
   struct LfPoolEntry* lf_pool;
   int lf_pool_n, lf_pool_cap;
   int64_t lf_pool_bytes;
+  // Jacobi-preconditioned MINRES (minres_precond.hip): the 7 vectors of mr_ws and a ring of two z = M^-1 r2
+  double* pmr_ws;
+  int64_t pmr_ws_n;
 };
 
 struct LfPoolEntry {

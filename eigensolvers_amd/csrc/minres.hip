@@ -38,19 +38,6 @@ void hipeig_phase_mark(hipeig_ctx* c, int k);
 
 #include "minres_device.h"
 
-// KD's element: w = (v - oldeps*w1 - delta*w2)*denom ; x += phi*w with v = s_old*r2old.  One definition for the
-// stand-alone kernel and for the epilogue form, so that both evaluate the same expression.
-struct MinresKd {
-  double s_old, oldeps, delta, denom, phi;
-  __device__ __forceinline__ void apply(double r2old, double a1, double a2, double& wn, double& xv) const {
-    // spelled out with explicit fused operations (and contraction off) so that every instantiation - the stand-alone
-    // kernel and the epilogue of each sweep layout - rounds identically: the two forms then agree bit for bit
-#pragma clang fp contract(off)
-    wn = fma(-delta, a2, fma(-oldeps, a1, s_old * r2old)) * denom;
-    xv = fma(phi, wn, xv);
-  }
-};
-
 struct MinresRowEpilogue {
   double sigma, sign, s, c1;
   int use_r1;

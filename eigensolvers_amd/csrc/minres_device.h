@@ -101,3 +101,17 @@ static inline void minres_init_state(MinresState* h, double bb) {
   h->gmin = 1.7976931348623157e308;
   h->s = 1.0 / h->beta;
 }
+
+// KD's element: w = (v - oldeps*w1 - delta*w2)*denom ; x += phi*w with v = s_old*r2old (with a preconditioner: s_old*z_old,
+// minres_precond.hip).  One definition for the stand-alone kernels and for the epilogue forms, so that all evaluate the
+// same expression.
+struct MinresKd {
+  double s_old, oldeps, delta, denom, phi;
+  __device__ __forceinline__ void apply(double r2old, double a1, double a2, double& wn, double& xv) const {
+    // spelled out with explicit fused operations (and contraction off) so that every instantiation - the stand-alone
+    // kernel and the epilogue of each sweep layout - rounds identically: the two forms then agree bit for bit
+#pragma clang fp contract(off)
+    wn = fma(-delta, a2, fma(-oldeps, a1, s_old * r2old)) * denom;
+    xv = fma(phi, wn, xv);
+  }
+};

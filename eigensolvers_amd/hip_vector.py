@@ -26,6 +26,37 @@ _ORTHO_METHODS = {"mgs": 0, "cgs2": 1}
 # beyond it (measured: tools/gcrot_block_bench.py, profiles/r06_gcrot_block_bench.jsonl).
 BLOCK_SOLVE_MIN_GCROT = 2
 BLOCK_SOLVE_MIN_GCROT_LONG = 4
+PRECONDITIONER_FLOOR_DEFAULT = 1e-8      # relative; only a guard against h_ii == sigma, not a tuned value
+
+
+def _preconditioner(o, sigma=None, x0=None, ctx=None):
+    """``o["preconditioner"]`` of a ``linearSystemArgs`` dict, validated: ``None`` or ``"jacobi"``.  The key belongs to
+    the real-shift single-vector MINRES solve on one GPU; every other combination raises instead of doing something else."""
+    pre = o.get("preconditioner")
+    if pre is None:
+        return None
+    if pre != "jacobi":
+        raise ValueError(f'linearSystemArgs["preconditioner"] must be None or "jacobi", got {pre!r}')
+    name = o["linearSolver"]
+    if name in ("minres_shifted", "lanczos_filter"):
+        raise ValueError(f'linearSystemArgs["preconditioner"] cannot be combined with linearSolver={name!r}: that path takes '
+                         "every shift from ONE Krylov space of H, and a preconditioner destroys the shift invariance of "
+                         "the Krylov space it rests on")
+    if name != "minres":
+        raise ValueError(f'linearSystemArgs["preconditioner"] is honoured by linearSolver="minres" only, not {name!r}')
+    if sigma is not None and (isinstance(sigma, complex) or np.iscomplexobj(sigma)):
+        raise ValueError('linearSystemArgs["preconditioner"] needs a real shift: complex shifts are solved by GCROT, '
+                         "which takes no preconditioner here")
+    floor = o.get("preconditionerFloor", PRECONDITIONER_FLOOR_DEFAULT)
+    if not (isinstance(floor, (int, float, np.floating, np.integer)) and 0.0 <= float(floor) < float("inf")):
+        raise ValueError(f'linearSystemArgs["preconditionerFloor"] must be a finite number >= 0, got {floor!r}')
+    if x0 is not None:
+        raise NotImplementedError("the preconditioned MINRES starts from x = 0: an initial guess (x0) is not implemented "
+                                  "with a preconditioner")
+    if ctx is not None and ctx.collectives:
+        raise NotImplementedError("the preconditioned MINRES runs on one GPU: a context with collectives (a row "
+                                  "partition, or its HIPEIG_FORCE_COLLECTIVES rehearsal) is not implemented")
+    return pre
 
 
 def _ptr_table(bufs):
@@ -286,6 +317,35 @@ class HipCsrOperator:
                   C.c_uint64(p["seed"]), p["eps"], C.c_uint32(p["thresh24"]),
                   t.ctypes.data_as(C.POINTER(C.c_double)), len(t), C.byref(h))
         return cls(ctx, h)
+
+    def diagonal(self):
+        """Device buffer with ``d_i`` = the sum of the stored ``(i, i)`` entries of local row ``i`` (0 where a row stores
+        none; duplicate entries are separate stored elements and are summed in stored order).  Taken once per operator."""
+        d = getattr(self, "_diagonal", None)
+        if d is None:
+            d = self.ctx.alloc(self.nrows)
+            _lib.call("hipeig_csr_diagonal", self.ctx.handle, self.handle, d.ptr)
+            self._diagonal = d
+        return d
+
+    def jacobi_inverse(self, sigma, floor=PRECONDITIONER_FLOOR_DEFAULT):
+        """Device buffer with ``minv_i = 1 / max(t_i, floor * max_j t_j)``, ``t_i = |sigma - d_i|``: the ``M^-1`` of the
+        Jacobi-preconditioned MINRES.  Kept for the latest ``(sigma, floor)``: a Lanczos run has one shift, so it is built
+        once.  ``ValueError`` where an element would not be finite (``h_ii == sigma`` with ``floor = 0``)."""
+        key = (float(sigma), float(floor))
+        cached = getattr(self, "_jacobi", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        d = self.diagonal()
+        minv = self.ctx.alloc(self.nrows)
+        try:
+            _lib.call("hipeig_jacobi_inverse", self.ctx.handle, self.nrows, d.ptr, key[0], key[1], minv.ptr)
+        except _lib.HipEigError as exc:
+            if "not finite" in str(exc):
+                raise ValueError(str(exc)) from None
+            raise
+        self._jacobi = (key, minv)
+        return minv
 
     VARIANTS = {0: "none", 1: "csr-vector", 2: "csr-stream", 3: "column-window-blocked(wave)",
                 4: "column-window-blocked(workgroup)", 5: "column-window-blocked(workgroup, fixed-point)"}
@@ -659,8 +719,21 @@ class HipVector(AbstractVector):
 
     @staticmethod
     def solve(H, b, sigma, x0=None, opType="her", reverseGF=False):
+        """``(sigma I - H) x = b`` (``reverseGF``: ``(H - sigma I) x = b``) with the solver and limits of
+        ``b.options["linearSystemArgs"]`` (numpyVector.py:147-178); ``UserWarning`` on non-convergence.
+
+        ``linearSystemArgs["preconditioner"] = "jacobi"`` (default ``None``; with ``linearSolver="minres"``, a real shift,
+        no ``x0``, one GPU - anything else raises) runs SciPy's ``minres(A, b, M=...)`` with the diagonal
+        ``M = diag(max(|sigma - h_ii|, f * max_j |sigma - h_jj|))``, ``f = linearSystemArgs["preconditionerFloor"]``
+        (relative, ``>= 0``, default 1e-8: only a guard against ``h_ii == sigma``; ``f = 0`` with an exact hit raises
+        ``ValueError``).  ``reverseGF`` flips the sign only, ``M`` is the same.  ``linear_tol`` is then tested in SciPy's
+        PRECONDITIONED quantities - ``beta1 = sqrt(<b, M^-1 b>)`` and the residual estimate ``phibar`` in the ``M^-1`` norm,
+        exactly what ``scipy.sparse.linalg.minres(A, b, M=...)`` does - so the 2-norm residual at the stop is not the plain
+        solve's.  ``last_solve_stats`` keeps its keys and gains ``"preconditioner": "jacobi"``.  It pays on diagonally
+        dominant operators and buys nothing on others."""
         if not isinstance(H, HipCsrOperator):
             raise TypeError("HipVector.solve needs a HipCsrOperator (device-resident CSR)")
+        pre = _preconditioner(b.options["linearSystemArgs"], sigma, x0, b.ctx)
         if isinstance(b, HipComplexVector):                 # HipVector(complex array) is a HipComplexVector: same entry point
             return HipComplexVector.solve(H, b, sigma, x0, opType, reverseGF)
         if b.options["linearSystemArgs"]["linearSolver"] == "minres_shifted":
@@ -705,7 +778,11 @@ class HipVector(AbstractVector):
         out = b.ctx.alloc(b._buf.n)
         info = C.c_int()
         stats = (C.c_double * 8)()
-        if x0 is None:
+        if pre == "jacobi":
+            minv = H.jacobi_inverse(float(sigma), float(o.get("preconditionerFloor", PRECONDITIONER_FLOOR_DEFAULT)))
+            _lib.call("hipeig_minres_jacobi", b.ctx.handle, H.handle, float(sigma), -1.0 if reverseGF else 1.0,
+                      b._buf.ptr, minv.ptr, out.ptr, float(o["linear_tol"]), int(o["linearIter"]), C.byref(info), stats)
+        elif x0 is None:
             _lib.call("hipeig_minres", b.ctx.handle, H.handle, float(sigma), -1.0 if reverseGF else 1.0,
                       b._buf.ptr, out.ptr, float(o["linear_tol"]), int(o["linearIter"]), C.byref(info), stats)
         else:               # scipy.sparse.linalg.minres(linOp, b, x0): r1 = b - A x0, the iterate starts at x0
@@ -715,6 +792,8 @@ class HipVector(AbstractVector):
         res.last_solve_stats = {"iterations": int(stats[0]), "istop": int(stats[1]), "rnorm": stats[2],
                                 "Anorm": stats[3], "ynorm": stats[4], "test1": stats[5],
                                 "test2": stats[6], "Acond": stats[7]}
+        if pre is not None:
+            res.last_solve_stats["preconditioner"] = pre
         if b.ctx.nranks > 1 or os.environ.get("HIPEIG_FORCE_COLLECTIVES", "0") not in ("", "0"):
             cs = (C.c_int64 * 4)()
             _lib.call("hipeig_comm_stats", b.ctx.handle, cs)
@@ -730,6 +809,7 @@ class HipVector(AbstractVector):
         """All of ``shifts`` for one right-hand side from one Lanczos run (``shifted_minres.solve_shifts``); the hook
         ``feastDiagonalization`` looks for when ``linearSolver`` is ``"minres_shifted"``."""
         from .shifted_minres import solve_shifts
+        _preconditioner(b.options["linearSystemArgs"])
         return solve_shifts(H, b, shifts, reverseGF=reverseGF)
 
     @staticmethod
@@ -744,6 +824,8 @@ class HipVector(AbstractVector):
         from .lanczos_filter import lanczos_filter
         B = list(B)
         o = B[0].options if B else {}
+        if B:
+            _preconditioner(o["linearSystemArgs"])
         if o.get("lanczosBasisPrefix") and o.get("lanczosBasis", "recompute") != "keep":
             raise ValueError('"lanczosBasisPrefix" keeps a prefix of a kept basis: it needs "lanczosBasis": "keep"')
         if o.get("lanczosBasisPrecision", "fp64") == "fp32" and o.get("lanczosBasis", "recompute") != "keep":
@@ -773,8 +855,24 @@ class HipVector(AbstractVector):
         each with its shift.  ``onSolution(i, x_i)``, when given, is called the moment solve i has ended (in the order
         the solves end) and the returned list then holds ``None`` in place of the solutions handed out, so that a caller
         who folds each solution into a sum never holds all of them.  ``poolStats``, a dict, receives the pool's record
-        (width, rounds, block products by live operands, products and outer iterations per solve) when the pool ran."""
+        (width, rounds, block products by live operands, products and outer iterations per solve) when the pool ran.
+
+        With ``linearSystemArgs["preconditioner"]`` set the solves are the one-by-one ``solve`` calls whatever the block
+        size: the lock-step block kernel has no preconditioned form yet."""
         bs = list(bs)
+        if bs and _preconditioner(bs[0].options["linearSystemArgs"]) is not None:
+            # one by one whatever the block size: every refusal and result is that of solve()
+            shifts = list(sigma) if np.ndim(sigma) > 0 else [sigma] * len(bs)
+            if len(shifts) != len(bs):
+                raise ValueError(f"{len(shifts)} shifts for {len(bs)} right-hand sides")
+            out = []
+            for i, (b, z) in enumerate(zip(bs, shifts)):
+                xs = HipVector.solve(H, b, z, x0, opType, reverseGF)
+                if onSolution is not None:
+                    onSolution(i, xs)
+                    xs = None
+                out.append(xs)
+            return out
         if np.ndim(sigma) > 0:
             return HipVector._solve_block_shifts(H, bs, list(sigma), x0, opType, reverseGF, onSolution, poolStats)
         if onSolution is not None:
@@ -1246,6 +1344,7 @@ class HipComplexVector(AbstractVector):
         if not isinstance(H, HipCsrOperator):
             raise TypeError("HipComplexVector.solve needs a HipCsrOperator (device-resident CSR)")
         o = b.options["linearSystemArgs"]
+        _preconditioner(o, sigma, x0, b.ctx)
         if o["linearSolver"] == "minres_shifted":
             raise NotImplementedError("linearSolver='minres_shifted' takes a real right-hand side (its Lanczos run is real)")
         if o["linearSolver"] == "pardiso":

@@ -1,0 +1,160 @@
+"""NumPy twin of the Jacobi-preconditioned device MINRES (``csrc/minres_precond.hip``).
+
+``scipy.sparse.linalg.minres(A, b, M=...)`` (SciPy 1.15.3) restated for a diagonal ``M^-1 = diag(minv)`` in the order of
+evaluation the device uses: ``z = minv * r2`` is a vector of its own, the Lanczos vector is ``v = z / beta`` and
+``beta^2 = <r2, z>``; every scalar recurrence and stopping test is that of the plain solver.  The reference calls SciPy's
+``minres`` without ``M`` (numpyVector.py:163), so this path has no counterpart there; SciPy itself is the referee
+(``tests/test_precond_minres_cpu.py``).
+
+``jacobi_inverse_host`` is the NumPy statement of ``hipeig_jacobi_inverse`` and ``csr_diagonal_host`` that of
+``hipeig_csr_diagonal``.
+"""
+import math
+
+import numpy as np
+
+
+def csr_diagonal_host(A):
+    """``d_i`` = sum of the stored ``(i, i)`` entries of row ``i`` of a scipy CSR matrix in stored order (duplicate
+    entries are separate stored elements), 0 where a row stores none."""
+    n = A.shape[0]
+    rows = np.repeat(np.arange(n), np.diff(A.indptr))
+    on = A.indices == rows
+    d = np.zeros(n)
+    np.add.at(d, rows[on], A.data[on])                   # unbuffered: adds in stored order
+    return d
+
+
+def jacobi_inverse_host(diag, sigma, floor=1e-8):
+    """``minv_i = 1 / max(t_i, floor * max_j t_j)`` with ``t_i = |sigma - diag_i|``; ``floor`` is relative and ``>= 0``.
+    Raises ``ValueError`` where an element would not be finite (a diagonal entry equal to ``sigma`` with ``floor = 0``, a
+    non-finite diagonal entry)."""
+    floor = float(floor)
+    if not (0.0 <= floor < math.inf):
+        raise ValueError(f"the relative floor must be finite and >= 0, got {floor!r}")
+    t = np.abs(float(sigma) - np.asarray(diag, dtype=np.float64))
+    if t.size == 0:
+        return t
+    tmax = math.inf if np.isnan(t).any() else float(t.max())
+    tmin = float(np.nanmin(t))
+    floor_abs = floor * tmax if tmax < math.inf else math.inf
+    mmin = max(tmin, floor_abs)
+    if not (tmax < math.inf) or not (floor_abs < math.inf) or not (mmin > 0.0) or not (1.0 / mmin < math.inf):
+        raise ValueError(f"Jacobi preconditioner is not finite: max |sigma - d_i| = {tmax:g}, min = {tmin:g}, relative "
+                         f"floor {floor:g} (a diagonal entry equal to sigma needs a floor > 0)")
+    return 1.0 / np.maximum(t, floor_abs)
+
+
+def minres_jacobi_host(matvec, b, minv, rtol=1e-5, maxiter=None, trace=None):
+    """``scipy.sparse.linalg.minres(A, b, M=diags(minv), rtol=rtol, maxiter=maxiter)`` from ``x = 0``.
+
+    Returns ``(x, info, itn, istop)``: ``info`` is ``maxiter`` when the iteration limit was the stopping reason
+    (``istop == 6``) and 0 otherwise.  ``trace``, a list, receives one record of scalars per iteration.  ``rtol`` is tested
+    in SciPy's preconditioned quantities: ``beta1 = sqrt(<b, M^-1 b>)``, ``rnorm = phibar`` in the ``M^-1`` norm."""
+    b = np.asarray(b, dtype=np.float64)
+    minv = np.asarray(minv, dtype=np.float64)
+    n = b.shape[0]
+    if maxiter is None:
+        maxiter = 5 * n
+    eps = np.finfo(np.float64).eps
+    x = np.zeros(n)
+
+    r2 = b.copy()
+    z = minv * r2                                       # start kernel
+    beta1 = float(np.dot(r2, z))
+    if beta1 < 0:
+        raise ValueError("indefinite preconditioner")
+    if beta1 == 0.0:
+        return x, 0, 0, 0
+    beta1 = math.sqrt(beta1)
+
+    oldb = 0.0
+    beta = beta1
+    dbar = 0.0
+    epsln = 0.0
+    phibar = beta1
+    tnorm2 = 0.0
+    gmax = 0.0
+    gmin = np.finfo(np.float64).max
+    cs = -1.0
+    sn = 0.0
+    w = np.zeros(n)
+    w2 = np.zeros(n)
+    r1 = r2
+    istop = 0
+    itn = 0
+
+    while itn < maxiter:
+        itn += 1
+        s = 1.0 / beta
+        v = s * z                                       # KA': the sweep gathers z
+        y = matvec(v)
+        if itn >= 2:
+            y = y - (beta / oldb) * r1
+        alfa = float(np.dot(v, y))
+        y = y - (alfa / beta) * r2                      # KC'
+        r1 = r2
+        r2 = y
+        z = minv * r2
+        oldb = beta
+        beta = float(np.dot(r2, z))
+        if beta < 0:
+            raise ValueError("non-symmetric matrix")
+        beta = math.sqrt(beta)
+        tnorm2 += alfa * alfa + oldb * oldb + beta * beta
+        if itn == 1 and beta / beta1 <= 10 * eps:
+            istop = -1
+
+        oldeps = epsln
+        delta = cs * dbar + sn * alfa
+        gbar = sn * dbar - cs * alfa
+        epsln = sn * beta
+        dbar = -cs * beta
+        root = math.sqrt(gbar * gbar + dbar * dbar)
+
+        gamma = max(math.sqrt(gbar * gbar + beta * beta), eps)
+        cs = gbar / gamma
+        sn = beta / gamma
+        phi = cs * phibar
+        phibar = sn * phibar
+
+        denom = 1.0 / gamma                             # KD
+        w1 = w2
+        w2 = w
+        w = (v - oldeps * w1 - delta * w2) * denom
+        x = x + phi * w
+
+        gmax = max(gmax, gamma)
+        gmin = min(gmin, gamma)
+
+        Anorm = math.sqrt(tnorm2)
+        ynorm = math.sqrt(float(np.dot(x, x)))
+        epsx = Anorm * ynorm * eps
+        rnorm = phibar
+        test1 = math.inf if (ynorm == 0 or Anorm == 0) else rnorm / (Anorm * ynorm)
+        test2 = math.inf if Anorm == 0 else root / Anorm
+        Acond = gmax / gmin
+
+        if istop == 0:
+            if 1 + test2 <= 1:
+                istop = 2
+            if 1 + test1 <= 1:
+                istop = 1
+            if itn >= maxiter:
+                istop = 6
+            if Acond >= 0.1 / eps:
+                istop = 4
+            if epsx >= beta1:
+                istop = 3
+            if test2 <= rtol:
+                istop = 2
+            if test1 <= rtol:
+                istop = 1
+        if trace is not None:
+            trace.append(dict(itn=itn, alfa=alfa, beta=beta, rnorm=rnorm, ynorm=ynorm,
+                              Anorm=Anorm, test1=test1, test2=test2, istop=istop))
+        if istop != 0:
+            break
+
+    info = maxiter if istop == 6 else 0
+    return x, info, itn, istop

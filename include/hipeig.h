@@ -299,6 +299,26 @@ int hipeig_minres_x0(hipeig_ctx* ctx, hipeig_csr* A, double sigma, double sign, 
                      const double* x0, double* x, double rtol, int maxiter, int* info,
                      double out_stats[8]);
 
+/* ---- Jacobi-preconditioned MINRES (opt-in: linearSystemArgs["preconditioner"] = "jacobi") ---- */
+/* The reference passes no preconditioner (numpyVector.py:163 calls scipy.sparse.linalg.minres without M), so these three
+ * restate SciPy, not the reference: scipy.sparse.linalg.minres(A, b, M=diags(minv)) of SciPy 1.15.3.
+ *
+ * d[i] = sum of the stored (i, i) entries of local row i in stored order (duplicate (row, col) entries are separate stored
+ * elements), 0 when the row stores none: what scipy.sparse's A.diagonal() returns.  On a row slice the diagonal column of
+ * local row i is row_offset + i.  Asynchronous.                                                                    */
+int hipeig_csr_diagonal(hipeig_ctx* ctx, hipeig_csr* A, double* d);
+/* minv[i] = 1 / max(t_i, floor_rel * max_j t_j) with t_i = |sigma - d[i]|: the inverse of the diagonal of |sigma*I - H|
+ * (Davidson's correction), the M^-1 that SciPy's minres takes as `M`.  Fails (hipeig_last_error) instead of writing when
+ * an element would not be finite: a d[i] equal to sigma with floor_rel = 0, a non-finite d[i].                        */
+int hipeig_jacobi_inverse(hipeig_ctx* ctx, int64_t n, const double* d, double sigma, double floor_rel,
+                          double* minv);
+/* hipeig_minres with SciPy's M: the Lanczos vectors are built from z = minv (.) r2 and beta^2 = <r2, z>, so rtol is tested
+ * in SciPy's preconditioned quantities (beta1 = sqrt(<b, M^-1 b>), rnorm = phibar in the M^-1 norm).  info and out_stats
+ * as in hipeig_minres.  One GPU, whole vectors, a square operator: a context with collectives is refused.          */
+int hipeig_minres_jacobi(hipeig_ctx* ctx, hipeig_csr* A, double sigma, double sign, const double* b,
+                         const double* minv, double* x, double rtol, int maxiter, int* info,
+                         double out_stats[8]);
+
 /* linearSolver = "pardiso" (numpyVector.py:166-170: spsolve of sigma*I - H, kept by the reference "only for comparing
  * with fortran" - the 4 x 4 known-answer system of unittests/test_feast_fortran.py): x = (sign*(z I - H))^-1 b by
  * Gaussian elimination with partial pivoting in the LDS of one workgroup, n <= 96, z = zr + i zi.  b_im and x_im may be
