@@ -132,9 +132,12 @@ struct hipeig_ctx {
   const double** d_ptrs;     // device pointer tables for tall-skinny kernels
   const double** h_ptrs;     // pinned staging of the same
   size_t ptrs_count;
-  // MINRES workspace (7 vectors: r1 r2 y, w1 w2 w, x) cached across solves
+  // MINRES workspace cached across solves: 7 vectors (r1 r2 y, w1 w2 w, x), 9 once a Jacobi-preconditioned solve has run
+  // (a ring of two z = M^-1 r2 behind them); mr_ws_n is the vector length the buffer was allocated for, which fixes the
+  // vectors' stride until the buffer is allocated anew
   double* mr_ws;
   int64_t mr_ws_n;
+  int64_t mr_ws_doubles;
   // hipGraph of one 18-iteration MINRES chunk, replayed while its key (operator layout, shift,
   // tolerances, workspace) is unchanged
   hipGraphExec_t mr_graph;
@@ -200,9 +203,6 @@ struct hipeig_ctx {
   struct LfPoolEntry* lf_pool;
   int lf_pool_n, lf_pool_cap;
   int64_t lf_pool_bytes;
-  // Jacobi-preconditioned MINRES (minres_precond.hip): the 7 vectors of mr_ws and a ring of two z = M^-1 r2
-  double* pmr_ws;
-  int64_t pmr_ws_n;
 };
 
 struct LfPoolEntry {

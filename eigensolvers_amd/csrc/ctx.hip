@@ -92,7 +92,6 @@ extern "C" int hipeig_ctx_destroy(hipeig_ctx* c) {
   if (c->d_mrb_state) hipFree(c->d_mrb_state);
   if (c->h_mrb_state) hipHostFree(c->h_mrb_state);
   if (c->ms_ws) hipFree(c->ms_ws);
-  if (c->pmr_ws) hipFree(c->pmr_ws);
   if (c->h_ms_state) hipHostFree(c->h_ms_state);
   if (c->lf_ws) hipFree(c->lf_ws);
   if (c->h_lf_state) hipHostFree(c->h_lf_state);

@@ -22,46 +22,48 @@
 //     (round 2 took it as <y,y> - alfa^2 from the un-updated y, which cancels when the right-hand side is close to an
 //     eigenvector - restart vectors, converged Ritz vectors);
 //   * <v,y> and the <x,x> of the KD riding on the sweep share ONE all-reduce of two doubles.
+//
+// Jacobi preconditioner (PRECOND, opt-in through hipeig_minres_jacobi; recurrence, byte model and limits: DESIGN.md 3.2b):
+// the Lanczos vector is built from z = minv (.) r2 instead of r2 and beta^2 = <r2, z>.  z_k is materialised (a ring of
+// two), so KA gathers z_k where the plain solve gathers r2, KC also writes z_{k+1} = minv (.) y and reduces <y, z_{k+1}>,
+// and the riding KD reads z_{k-1} where the plain one shares r1.  The scalar side (minres_device.h) is unchanged.
 #include <math.h>
-#include "spmv_device.h"
-
-CsrView hipeig_csr_view(const hipeig_csr* A);
-TcooView hipeig_tcoo_view(const hipeig_csr* A, const BlockedLayout& L);
-int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, int fixed, TcooView* last, bool* has_last,
-                          const double** xg, int* ncombine);
-int64_t hipeig_tcoow_part_stride(const hipeig_csr* A);
-int hipeig_tcoow_reserve(hipeig_ctx* c, const hipeig_csr* A);
-SweepGrid hipeig_sweep_grid(const hipeig_csr* A, int variant);
-int hipeig_csr_pick_variant(hipeig_ctx* c, hipeig_csr* A);
-size_t hipeig_tcoo_lds_bytes(const hipeig_csr* A);
-void hipeig_phase_mark(hipeig_ctx* c, int k);
-
+#include "sweep_launch.h"
 #include "minres_device.h"
 
+void hipeig_phase_mark(hipeig_ctx* c, int k);
+// minres_precond.hip: r2 = b, z = minv (.) b and *bz = <b, z> (synchronises; refuses <b, z> < 0)
+int hipeig_pmr_start(hipeig_ctx* c, int64_t n, const double* b, const double* minv, double* r2, double* z, int grid,
+                     const MinresRed& rc, double* bz);
+
+// Row epilogue of KA: v = s*src[r]; y = sign*(sigma*v - s*sum) - (beta/oldb)*r1[r]; <v,y>; and the KD of the iteration
+// before riding on this sweep.
+template <int PRECOND>
 struct MinresRowEpilogue {
   double sigma, sign, s, c1;
   int use_r1;
-  const double* __restrict__ r2l;   // local slice of r2 (v = s*r2)
+  const double* __restrict__ src;   // local slice of the gathered vector: r2, PRECOND: z_k (v = s*src)
   const double* __restrict__ r1;
   double* __restrict__ y;
-  // KD of the previous iteration riding on this sweep: r1 is the r2 it reads
+  // KD of the previous iteration: its vector is the r2 of that iteration = r1 of this sweep, PRECOND: z_{k-1}
   int do_kd;
   MinresKd kd;
+  const double* __restrict__ zold;
   const double* __restrict__ w1;
   const double* __restrict__ w2;
   double* __restrict__ w;
   double* __restrict__ x;
   double* xx;                       // running <x,x> of this thread
   __device__ __forceinline__ void row(int64_t r, double sum, double& acc) const {
-    const double v = s * r2l[r];
+    const double v = s * src[r];
     double yv = sign * (mul_rn(sigma, v) - s * sum);
-    const double r1v = (use_r1 || do_kd) ? r1[r] : 0.0;
+    const double r1v = (use_r1 || (!PRECOND && do_kd)) ? r1[r] : 0.0;
     if (use_r1) yv -= c1 * r1v;
     y[r] = yv;
     acc = fma(v, yv, acc);
     if (do_kd) {
       double wn, xv = x[r];
-      kd.apply(r1v, w1[r], w2[r], wn, xv);
+      kd.apply(PRECOND ? zold[r] : r1v, w1[r], w2[r], wn, xv);
       w[r] = wn; x[r] = xv;
       *xx = fma(xv, xv, *xx);
     }
@@ -71,6 +73,7 @@ struct MinresRowEpilogue {
 // What the KD riding on a KA launch needs besides the state record.
 struct MinresKdArgs {
   int do_kd;
+  const double* zold;               // PRECOND only
   const double* w1;
   const double* w2;
   double* w;
@@ -82,16 +85,16 @@ struct MinresKdArgs {
 // (T.raw_out holds T.part_base slabs of raw sums, see spmv_device.h) - same prologue, same epilogue.
 // FIXED = 1 (VARIANT 4 only): fixed-point accumulators, public kernel variant 5 (spmv_device.h).
 // `zero_xx`: a row-partitioned run all-reduces (<v,y>, <x,x>) as one record, so a sweep without a riding KD stores 0 there.
-template <int VARIANT, int FIXED = 0>
+template <int VARIANT, int FIXED, int PRECOND>
 __global__ void __launch_bounds__(VARIANT == 4 ? TCOOW_THREADS : HIPEIG_BLOCK)
 minres_ka_kernel(CsrView A, TcooView T, const double* __restrict__ xg, MinresArgs a, const MinresState* __restrict__ Sin,
-                 MinresState* __restrict__ Sout, const double* __restrict__ r2l,
+                 MinresState* __restrict__ Sout, const double* __restrict__ src,
                  const double* __restrict__ r1, double* __restrict__ y, MinresRed ra, MinresKdArgs kda, int zero_xx) {
   __shared__ double prod[VARIANT == 2 ? SPMV_NNZ_PER_BLOCK : 8];
   __shared__ double red[16];
   extern __shared__ double tcoo_lds[];
   MinresState S = *Sin;
-  MinresRowEpilogue epi;
+  MinresRowEpilogue<PRECOND> epi;
   epi.do_kd = 0;
   if (kda.do_kd) {
     // Sin is the record KC left: the scalar half of KD (minres_kd_kernel) happens here, its vector half in the
@@ -112,11 +115,11 @@ minres_ka_kernel(CsrView A, TcooView T, const double* __restrict__ xg, MinresArg
   epi.sigma = a.sigma; epi.sign = a.sign; epi.s = S.s;
   epi.use_r1 = S.itn >= 1;
   epi.c1 = epi.use_r1 ? S.beta / S.oldb : 0.0;
-  epi.r2l = r2l; epi.r1 = r1; epi.y = y;
+  epi.src = src; epi.r1 = r1; epi.y = y;
   double acc = 0.0, acc_xx = 0.0;
-  epi.w1 = kda.w1; epi.w2 = kda.w2; epi.w = kda.w; epi.x = kda.x; epi.xx = &acc_xx;
+  epi.zold = kda.zold; epi.w1 = kda.w1; epi.w2 = kda.w2; epi.w = kda.w; epi.x = kda.x; epi.xx = &acc_xx;
   if (VARIANT == 5) tcoow_combine_sweep(T.raw_out, T.part_base, T.part_stride, T.nrows, epi, acc);
-  else if (VARIANT == 4) tcoo_wg_sweep<MinresRowEpilogue, FIXED>(T, xg, epi, acc, tcoo_lds, red);
+  else if (VARIANT == 4) tcoo_wg_sweep<MinresRowEpilogue<PRECOND>, FIXED>(T, xg, epi, acc, tcoo_lds, red);
   else if (VARIANT == 3) tcoo_sweep(T, xg, epi, acc, tcoo_lds);
   else if (VARIANT == 2) csr_stream_sweep(A, xg, epi, acc, prod);
   else csr_vector_sweep(A, xg, epi, acc);
@@ -137,11 +140,14 @@ minres_ka_kernel(CsrView A, TcooView T, const double* __restrict__ xg, MinresArg
   }
 }
 
-// y -= (alfa/beta) r2 and <y,y>; with test_prev the stopping tests of the previous iteration first (its KD ran in the
-// epilogue of the sweep before this kernel and has left <x,x>).
+// y -= (alfa/beta) r2 and <y,y>; PRECOND: also z_{k+1} = minv (.) y, and <y, z_{k+1}> in place of <y,y>.  With test_prev
+// the stopping tests of the previous iteration first (its KD ran in the epilogue of the sweep before this kernel and has
+// left <x,x>).
+template <int PRECOND>
 __global__ void __launch_bounds__(HIPEIG_BLOCK)
 minres_kc_kernel(int64_t n, MinresArgs a, const MinresState* __restrict__ Sin, MinresState* __restrict__ Sout,
-                 const double* __restrict__ r2, double* __restrict__ y, MinresRed rc, int test_prev) {
+                 const double* __restrict__ r2, const double* __restrict__ minv, double* __restrict__ y,
+                 double* __restrict__ znext, MinresRed rc, int test_prev) {
   __shared__ double red[4];
   MinresState S = *Sin;
   if (test_prev && !S.done) {
@@ -154,23 +160,45 @@ minres_kc_kernel(int64_t n, MinresArgs a, const MinresState* __restrict__ Sin, M
   }
   S.alfa = a.pA[0];
   if (blockIdx.x == 0 && threadIdx.x == 0) *Sout = S;
-  const double c = S.alfa / S.beta;
   const int64_t n2 = n >> 1;
   const double2* r22 = reinterpret_cast<const double2*>(r2);
   double2* y2 = reinterpret_cast<double2*>(y);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
-    const double2 rv = r22[i];
-    double2 yv = y2[i];
-    yv.x -= c * rv.x; yv.y -= c * rv.y;
-    y2[i] = yv;
-    acc = fma(yv.x, yv.x, acc); acc = fma(yv.y, yv.y, acc);
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const double yv = y[n - 1] - c * r2[n - 1];
-    y[n - 1] = yv;
-    acc = fma(yv, yv, acc);
+  if constexpr (PRECOND) {
+    // explicit fused / separately rounded operations: the vector body and the tail round alike
+#pragma clang fp contract(off)
+    const double nc = -(S.alfa / S.beta);
+    const double2* m2 = reinterpret_cast<const double2*>(minv);
+    double2* z2 = reinterpret_cast<double2*>(znext);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
+      const double2 rv = r22[i], mv = m2[i];
+      double2 yv = y2[i], zv;
+      yv.x = fma(nc, rv.x, yv.x); yv.y = fma(nc, rv.y, yv.y);
+      zv.x = mv.x * yv.x; zv.y = mv.y * yv.y;
+      y2[i] = yv; z2[i] = zv;
+      acc = fma(yv.x, zv.x, acc); acc = fma(yv.y, zv.y, acc);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+      const double yv = fma(nc, r2[n - 1], y[n - 1]);
+      const double zv = minv[n - 1] * yv;
+      y[n - 1] = yv; znext[n - 1] = zv;
+      acc = fma(yv, zv, acc);
+    }
+  } else {
+    const double c = S.alfa / S.beta;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
+      const double2 rv = r22[i];
+      double2 yv = y2[i];
+      yv.x -= c * rv.x; yv.y -= c * rv.y;
+      y2[i] = yv;
+      acc = fma(yv.x, yv.x, acc); acc = fma(yv.y, yv.y, acc);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+      const double yv = y[n - 1] - c * r2[n - 1];
+      y[n - 1] = yv;
+      acc = fma(yv, yv, acc);
+    }
   }
   acc = block_reduce_sum(acc, red);
   if (threadIdx.x == 0) store_partial(rc.part + blockIdx.x, acc);
@@ -184,9 +212,11 @@ minres_kc_kernel(int64_t n, MinresArgs a, const MinresState* __restrict__ Sin, M
   }
 }
 
+// KD as its own kernel: the three-kernel form, and the last iteration of a chunk (nothing follows to ride on).
+// `vold`: r2 of the iteration, with a preconditioner its z.
 __global__ void __launch_bounds__(HIPEIG_BLOCK)
 minres_kd_kernel(int64_t n, MinresArgs a, const MinresState* __restrict__ Sin, MinresState* __restrict__ Sout,
-                 const double* __restrict__ r2old, const double* __restrict__ w1, const double* __restrict__ w2,
+                 const double* __restrict__ vold, const double* __restrict__ w1, const double* __restrict__ w2,
                  double* __restrict__ w, double* __restrict__ x, MinresRed rd) {
   __shared__ double red[4];
   MinresState S = *Sin;
@@ -201,7 +231,7 @@ minres_kd_kernel(int64_t n, MinresArgs a, const MinresState* __restrict__ Sin, M
   // ---- w = (v - oldeps*w1 - delta*w2)*denom ; x += phi*w ----
   const MinresKd kd{s_old, S.oldeps, S.delta, S.denom, S.phi};
   const int64_t n2 = n >> 1;
-  const double2* r2 = reinterpret_cast<const double2*>(r2old);
+  const double2* r2 = reinterpret_cast<const double2*>(vold);
   const double2* w12 = reinterpret_cast<const double2*>(w1);
   const double2* w22 = reinterpret_cast<const double2*>(w2);
   double2* wn2 = reinterpret_cast<double2*>(w);
@@ -220,7 +250,7 @@ minres_kd_kernel(int64_t n, MinresArgs a, const MinresState* __restrict__ Sin, M
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     const int64_t i = n - 1;
     double wn, xv = x[i];
-    kd.apply(r2old[i], w1[i], w2[i], wn, xv);
+    kd.apply(vold[i], w1[i], w2[i], wn, xv);
     w[i] = wn; x[i] = xv;
     acc = fma(xv, xv, acc);
   }
@@ -241,46 +271,75 @@ __global__ void minres_check_kernel(MinresArgs a, MinresState* __restrict__ S0) 
   if (threadIdx.x == 0) *S0 = S;
 }
 
-extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign, const double* b, const double* x0,
-                                double* x, double rtol, int maxiter, int* info, double out_stats[8]);
-
-extern "C" int hipeig_minres(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign, const double* b,
-                             double* x, double rtol, int maxiter, int* info, double out_stats[8]) {
-  return hipeig_minres_x0(c, A, sigma, sign, b, nullptr, x, rtol, maxiter, info, out_stats);
+template <int PRECOND>
+static int minres_ka_lds_limits(const SweepPlan& p) {
+  return sweep_set_lds_limits(p, (const void*)minres_ka_kernel<3, 0, PRECOND>, (const void*)minres_ka_kernel<4, 0, PRECOND>,
+                              (const void*)minres_ka_kernel<4, 1, PRECOND>);
 }
 
+// The solve behind hipeig_minres, hipeig_minres_x0 and hipeig_minres_jacobi.
 // x0 != NULL: SciPy's minres(A, b, x0) - r1 = b - A x0, the iterate starts at x0 (so ||x|| in the stopping tests
 // includes it), beta1 = ||r1||; beta1 == 0 returns x0, b == 0 returns b (scipy.sparse.linalg.minres, the x0 branch).
-extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign, const double* b, const double* x0,
-                                double* x, double rtol, int maxiter, int* info, double out_stats[8]) {
+// minv != NULL: the Jacobi-preconditioned solve (PRECOND kernels, one GPU, no x0).
+static int minres_solve(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign, const double* b, const double* x0,
+                        const double* minv, double* x, double rtol, int maxiter, int* info, double out_stats[8]) {
   HIPEIG_REQUIRE(info != nullptr, "null info");
   HIPEIG_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
   HIPEIG_REQUIRE(maxiter >= 1, "maxiter must be positive");
   HIPEIG_REQUIRE(b != x, "x must not alias b");
   const int64_t n = A->nrows;
-  HIPEIG_REQUIRE(c->collectives || A->nrows == A->ncols, "the inner solve needs a square operator (or a row partition)");
   *info = 0;
   if (out_stats) memset(out_stats, 0, 8 * sizeof(double));
-  double bb = 0.0;
-  if (hipeig_dot(c, n, b, b, &bb)) return 1;
-  if (bb == 0.0) return hipeig_vec_fill(c, x, n, 0.0);            // beta1 == 0 (or b == 0): the exact solution is x = 0 = b
+  double bb = 0.0;                                                  // beta1^2
+  if (minv) {
+    if (n == 0) return 0;
+  } else {
+    if (hipeig_dot(c, n, b, b, &bb)) return 1;
+    if (bb == 0.0) return hipeig_vec_fill(c, x, n, 0.0);            // beta1 == 0 (or b == 0): the exact solution is x = 0 = b
+  }
 
-  // workspace: R[3] (r1, r2, y rotate), W[3] (w1, w2, w rotate) and the iterate xw.  The iterate
-  // lives in the workspace so that every kernel argument of a chunk is the same from solve to
-  // solve, which is what lets the captured chunk be replayed; it is copied to x at the end.
-  if (c->mr_ws_n < n) {
+  // workspace: R[3] (r1, r2, y rotate), W[3] (w1, w2, w rotate), the iterate xw and, with a preconditioner, the ring Z[2]
+  // of z = minv (.) r2.  The iterate lives in the workspace and the stride comes from the ALLOCATED length (mr_ws_n changes
+  // only where the buffer does), so that every kernel argument of a chunk is the same from solve to solve, which is what
+  // lets the captured chunk be replayed; it is copied to x at the end.
+  const int64_t nvec = minv ? 9 : 7;
+  if (n > c->mr_ws_n || c->mr_ws_doubles < nvec * ((c->mr_ws_n + 31) & ~(int64_t)31)) {
+    if (c->mr_graph) { hipGraphExecDestroy(c->mr_graph); c->mr_graph = nullptr; }    // it has the old buffer and stride baked in
     if (c->mr_ws) HIPEIG_CHECK(hipFree(c->mr_ws));
-    c->mr_ws = nullptr; c->mr_ws_n = 0;
-    const int64_t npad = (n + 31) & ~(int64_t)31;
-    HIPEIG_CHECK(hipMalloc((void**)&c->mr_ws, (size_t)npad * 7 * sizeof(double)));
-    c->mr_ws_n = n;
+    const int64_t nalloc = (n > c->mr_ws_n) ? n : c->mr_ws_n;
+    const int64_t doubles = nvec * ((nalloc + 31) & ~(int64_t)31);
+    c->mr_ws = nullptr; c->mr_ws_doubles = 0; c->mr_ws_n = 0;
+    HIPEIG_CHECK(hipMalloc((void**)&c->mr_ws, (size_t)doubles * sizeof(double)));
+    c->mr_ws_doubles = doubles; c->mr_ws_n = nalloc;
   }
   const int64_t npad = (c->mr_ws_n + 31) & ~(int64_t)31;
-  double* R[3] = {c->mr_ws, c->mr_ws + npad, c->mr_ws + 2 * npad};
-  double* W[3] = {c->mr_ws + 3 * npad, c->mr_ws + 4 * npad, c->mr_ws + 5 * npad};
-  double* xw = c->mr_ws + 6 * npad;
+  double* ws = c->mr_ws;
+  double* R[3] = {ws, ws + npad, ws + 2 * npad};
+  double* W[3] = {ws + 3 * npad, ws + 4 * npad, ws + 5 * npad};
+  double* xw = ws + 6 * npad;
+  double* Z[2] = {ws + 7 * npad, ws + 8 * npad};                    // only with a preconditioner
   HIPEIG_CHECK(hipMemsetAsync(W[0], 0, (size_t)npad * 4 * sizeof(double), c->stream));   // W[0..2] and xw
-  if (x0) {
+
+  int per_thread = 24;       // measured (tools/experiments/mr_grid_sweep.sh): 4 / 8 / 16 / 24 / 32 / 64 elements per thread -> 0.138 / 0.136 / 0.134 / 0.1335 / 0.135 / 0.140 ms per iteration at N = 1e6, 2.32 / 2.24 / 2.23 / 2.21 / 2.22 / 2.20 at N = 1e7: the fixed cost of a workgroup (state record, ticket), not the grid cap, is what these kernels feel
+  if (const char* e = getenv("HIPEIG_MR_PER_THREAD")) per_thread = atoi(e) > 0 ? atoi(e) : 24;     // tuning knob
+  const int gE = grid_wide(n, per_thread);                   // element-wise kernels: their reductions finish in the last workgroup
+  // partial-sum areas (HIPEIG_WIDE_PARTIALS apart) and the totals their last workgroups leave
+  double* pA = c->d_partials;
+  double* pC = c->d_partials + HIPEIG_WIDE_PARTIALS;
+  double* pD = c->d_partials + 2 * HIPEIG_WIDE_PARTIALS;
+  double* tot = c->d_scalars + SC_MINRES_TOT;                         // [0] <v,y>, [1] <x,x> (one all-reduce record), [2] <y,y> (PRECOND: <y,z>), [4..5] end-of-solve flush
+  unsigned* cntA = c->d_counters + 0;
+  unsigned* cntC = c->d_counters + HIPEIG_TICKET_WORDS;
+  unsigned* cntD = c->d_counters + 2 * HIPEIG_TICKET_WORDS;
+  const MinresRed redC{pC, pC, gE, (unsigned)gE, cntC, tot + 2, nullptr};
+  const MinresRed redD{pD, pD, gE, (unsigned)gE, cntD, tot + 1, nullptr};
+  HIPEIG_CHECK(hipMemsetAsync(tot, 0, 8 * sizeof(double), c->stream));
+
+  // the first residual r2_0 in R[0] (PRECOND: and z_0 in Z[0]) and beta1^2
+  if (minv) {
+    if (const int rc = hipeig_pmr_start(c, n, b, minv, R[0], Z[0], gE, redC, &bb)) return rc;
+    if (bb == 0.0) return hipeig_vec_fill(c, x, n, 0.0);            // beta1 == 0: SciPy returns x = 0
+  } else if (x0) {
     if (hipeig_spmv_shift(c, A, sigma, sign, x0, R[0])) return 1;          // A x0 with the two roundings of the lambda
     if (hipeig_axpby(c, n, 1.0, b, -1.0, R[0])) return 1;                  // r1 = b - A x0
     if (hipeig_dot(c, n, R[0], R[0], &bb)) return 1;
@@ -300,51 +359,24 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
   // the pinned record is rewritten by the first chunk's copy-back; the upload above must have read it
   if (hipeig_sync_checked(c)) return 4;
 
-  int variant = hipeig_csr_pick_variant(c, A);
-  if (variant < 0) return 1;
-  const bool fixed = (variant == 5);                    // TCOO-W with fixed-point accumulators: same structure as 4
-  if (fixed) variant = 4;
-  if (variant == 4 && hipeig_tcoow_reserve(c, A)) return 1;
-  const CsrView view = hipeig_csr_view(A);
-  const BlockedLayout& L = (variant == 4) ? A->w : A->t;    // the blocked copy of variants 3 / 4
-  const TcooView tview = hipeig_tcoo_view(A, L);
-  const size_t ldsA = (variant == 4) ? blocked_lds_bytes(A->w, 1) : (variant == 3) ? hipeig_tcoo_lds_bytes(A) : 0;
-  if (variant == 4) {
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_ka_kernel<4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_TCOOW_LDS_MAX));
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_ka_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_TCOOW_LDS_MAX));
-  }
-  if (variant == 3)
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_ka_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)HIPEIG_TCOO_LDS_MAX));
-  const SweepGrid sgA = hipeig_sweep_grid(A, variant);
-  const int gA = sgA.wgs, nsweepA = sgA.launches;
-  int per_thread = 24;       // measured (tools/experiments/mr_grid_sweep.sh): 4 / 8 / 16 / 24 / 32 / 64 elements per thread -> 0.138 / 0.136 / 0.134 / 0.1335 / 0.135 / 0.140 ms per iteration at N = 1e6, 2.32 / 2.24 / 2.23 / 2.21 / 2.22 / 2.20 at N = 1e7: the fixed cost of a workgroup (state record, ticket), not the grid cap, is what these kernels feel
-  if (const char* e = getenv("HIPEIG_MR_PER_THREAD")) per_thread = atoi(e) > 0 ? atoi(e) : 24;     // tuning knob
-  const int gE = grid_wide(n, per_thread);                   // element-wise kernels: their reductions finish in the last workgroup
-  // partial-sum areas (HIPEIG_WIDE_PARTIALS apart) and the totals their last workgroups leave
-  double* pA = c->d_partials;
-  double* pC = c->d_partials + HIPEIG_WIDE_PARTIALS;
-  double* pD = c->d_partials + 2 * HIPEIG_WIDE_PARTIALS;
-  double* tot = c->d_scalars + SC_MINRES_TOT;                         // [0] <v,y>, [1] <x,x> (one all-reduce record), [2] <y,y>, [4..5] end-of-solve flush
-  unsigned* cntA = c->d_counters + 0;
-  unsigned* cntC = c->d_counters + HIPEIG_TICKET_WORDS;
-  unsigned* cntD = c->d_counters + 2 * HIPEIG_TICKET_WORDS;
-  const bool dist = c->collectives != 0;
-  MinresArgs a;
-  a.sigma = sigma; a.sign = sign; a.rtol = rtol; a.maxiter = maxiter;
-  const bool split = (variant == 4) && A->w.csplit > 1;      // raw slabs + combine launch
   // combine launch of a column-split sweep (slab of a many-GPU run): rows per thread.  It carries the whole KA epilogue with
   // the riding KD (10 streams + the slabs), not a 2-stream update: 24 / 12 / 8 / 4 / 2 rows per thread -> 0.177 / 0.160 /
   // 0.156 / 0.160 / 0.166 ms per iteration (N = 1e6, 5 splits forced; profiles/r04_minres_combine_grid.txt)
   int ct = 8;
   if (const char* e = getenv("HIPEIG_MR_COMBINE_PER_THREAD")) ct = atoi(e) > 0 ? atoi(e) : 8;   // tuning knob
-  const int gC = grid_wide(n, ct);
-  const int nPA = split ? gC : gA * nsweepA;                 // partial <v,y> sums one iteration leaves in pA
-  HIPEIG_REQUIRE(nPA <= HIPEIG_WIDE_PARTIALS, "too many sweeps for the partial-sum buffer");
+  SweepPlan plan;
+  if (const int rc = sweep_plan_build(c, A, ct, &plan)) return rc;
+  // column splits serve the slabs of row-partitioned runs, which the preconditioned solve does not take
+  HIPEIG_REQUIRE(!(minv && plan.split), "the preconditioned solve does not take a column-split TCOO-W layout");
+  if (const int rc = minv ? minres_ka_lds_limits<1>(plan) : minres_ka_lds_limits<0>(plan)) return rc;
+  const auto kc_kernel = minv ? minres_kc_kernel<1> : minres_kc_kernel<0>;
+  const int nPA = plan.nPA;                                  // partial <v,y> sums one iteration leaves in pA
+  const bool dist = c->collectives != 0;
+  MinresArgs a;
+  a.sigma = sigma; a.sign = sign; a.rtol = rtol; a.maxiter = maxiter;
   a.pA = tot + 0; a.nA = 1;
   a.pD = tot + 1; a.nD = 1;
   a.pC = tot + 2; a.nC = 1; a.sC = 0;
-  HIPEIG_CHECK(hipMemsetAsync(tot, 0, 8 * sizeof(double), c->stream));
   c->mr_collectives = 0;
   // Row-partitioned run: <y,y> arrives as one share per rank in the scalar slots of the operand exchange (the pointer
   // is set per sweep: the direct backend alternates between two buffers)
@@ -355,62 +387,28 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
   const char* fk_env = getenv("HIPEIG_MINRES_FUSE_KD");
   const bool fuse_kd = dist || !(fk_env && atoi(fk_env) == 0);
 
-  const MinresRed redC{pC, pC, gE, (unsigned)gE, cntC, tot + 2, nullptr};
-  const MinresRed redD{pD, pD, gE, (unsigned)gE, cntD, tot + 1, nullptr};
-
-  // The operator sweep of iteration k (all variants).  `kd`: the pending KD of the previous iteration (do_kd = 0: none),
-  // `Sin`: the record the sweep starts from.
-  auto enqueue_ka = [&](double* r2, double* r1, double* yb, const MinresState* Sin, MinresKdArgs kd) -> int {
-    const double* xg = nullptr;
-    TcooView tv = tview;
+  // The operator sweep of iteration k (all variants) gathering `src` (r2, with a preconditioner z_k).  `kd`: the pending KD
+  // of the previous iteration (do_kd = 0: none), `Sin`: the record the sweep starts from.
+  auto enqueue_ka = [&](double* src, double* r1, double* yb, const MinresState* Sin, MinresKdArgs kd) -> int {
+    SweepOperand op;
+    if (sweep_prepare(c, A, plan, src, &op)) return 4;
+    HIPEIG_REQUIRE(!minv || (op.has_last && op.ncombine == 0), "unexpected split sweep");
     MinresArgs al = a;
-    const int zero_xx = dist ? 1 : 0;
-#define KA_LAUNCH(VAR, FIX, GRID, THREADS, LDS, TV, OFF)                                                            \
-    do {                                                                                                            \
-      MinresKdArgs kl = kd;                                                                                         \
-      kl.red = MinresRed{pD + (OFF), pD, nPA, (unsigned)nPA, cntD, tot + 1, nullptr};              \
-      const MinresRed ra{pA + (OFF), pA, nPA, (unsigned)nPA, cntA, tot + 0, nullptr};              \
-      hipLaunchKernelGGL((minres_ka_kernel<VAR, FIX>), dim3(GRID), dim3(THREADS), LDS, c->stream, view, TV, xg, al, Sin, V + 1, r2, r1, yb, ra, kl, zero_xx); \
-    } while (0)
-    if (variant == 4) {
-      bool has_last = true;
-      int ncombine = 0;                                           // own windows under the exchange, chunk by chunk behind it
-      if (hipeig_tcoow_run_plan(c, A, r2, fixed ? 1 : 0, &tv, &has_last, &xg, &ncombine)) return 4;
-      if (dist) { ++c->mr_collectives; al.pC = xg + slot0; al.nC = c->nranks; al.sC = slot_stride; }
-      if (has_last) {
-        for (int sw = 0; sw < nsweepA; ++sw) {
-          tv.unit_begin = sw * gA;
-          if (fixed) KA_LAUNCH(4, 1, gA, TCOOW_THREADS, ldsA, tv, sw * gA);
-          else KA_LAUNCH(4, 0, gA, TCOOW_THREADS, ldsA, tv, sw * gA);
-        }
-      }
-      if (ncombine) {
-        TcooView tc = tv;
-        tc.raw_out = c->ytmp;
-        tc.part_base = ncombine;                                  // number of slabs to add
-        KA_LAUNCH(5, 0, gC, HIPEIG_BLOCK, 0, tc, 0);
-      }
-      hipeig_phase_mark(c, 3);
-      return 0;
-    }
-    if (hipeig_allgather_x(c, A->gl, r2, n, &xg)) return 4;
-    if (dist) { ++c->mr_collectives; al.pC = xg + slot0; al.nC = c->nranks; al.sC = slot_stride; }
-    if (variant == 3) {
-      for (int sw = 0; sw < nsweepA; ++sw) {       // one launch per sweep; partials side by side
-        tv.unit_begin = sw * gA * 4;
-        KA_LAUNCH(3, 0, gA, HIPEIG_BLOCK, ldsA, tv, sw * gA);
-      }
-    } else if (variant == 1) {
-      KA_LAUNCH(1, 0, gA, HIPEIG_BLOCK, 0, tview, 0);
-    } else {
-      KA_LAUNCH(2, 0, gA, HIPEIG_BLOCK, 0, tview, 0);
-    }
-#undef KA_LAUNCH
+    if (dist) { ++c->mr_collectives; al.pC = op.xg + slot0; al.nC = c->nranks; al.sC = slot_stride; }
+    sweep_launch(c, plan, op, [&](auto v, auto f, int grid, int threads, size_t lds, const TcooView& tv, const double* xg, int off) {
+      kd.red = MinresRed{pD + off, pD, nPA, (unsigned)nPA, cntD, tot + 1, nullptr};
+      const MinresRed ra{pA + off, pA, nPA, (unsigned)nPA, cntA, tot + 0, nullptr};
+      const auto ka_kernel = minv ? minres_ka_kernel<decltype(v)::value, decltype(f)::value, 1> : minres_ka_kernel<decltype(v)::value, decltype(f)::value, 0>;
+      hipLaunchKernelGGL(ka_kernel, dim3(grid), dim3(threads), lds, c->stream, plan.view, tv, xg, al, Sin, V + 1, src, r1, yb, ra, kd, dist ? 1 : 0);
+    });
+    if (plan.variant == 4) hipeig_phase_mark(c, 3);
     return 0;
   };
 
-  const MinresKdArgs no_kd{0, nullptr, nullptr, nullptr, nullptr, MinresRed{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}};
-  // One iteration's launches on the compute stream (buffer roles rotate with period 3).  `first`: nothing is pending
+  const MinresKdArgs no_kd{0, nullptr, nullptr, nullptr, nullptr, nullptr, MinresRed{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}};
+  // The vector iteration k builds its Lanczos vector from: r2 = R[k % 3], with a preconditioner z_k (period 2)
+  auto lanczos_src = [&](int k) -> double* { return minv ? Z[k % 2] : R[k % 3]; };
+  // One iteration's launches on the compute stream (R and W rotate with period 3).  `first`: nothing is pending
   // from the iteration before (one GPU: the first iteration of a chunk - the chunk before ended with a stand-alone KD;
   // partitioned run: only the very first iteration, the pending KD is carried over the chunk boundary).
   auto enqueue_iteration = [&](int k, bool first) -> int {
@@ -420,36 +418,37 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
     double* wn = W[k % 3];
     double* w1 = W[(k + 1) % 3];
     double* w2 = W[(k + 2) % 3];
+    double* src = lanczos_src(k);
+    double* zn = minv ? Z[(k + 1) % 2] : nullptr;                // z_{k-1} until KC(k) writes z_{k+1} there
     if (fuse_kd) {
-      // KD(k-1): w = W[(k-1)%3] from w1 = W[k%3], w2 = W[(k+1)%3] and r2 of that iteration = this one's r1
+      // KD(k-1): w = W[(k-1)%3] from w1 = W[k%3], w2 = W[(k+1)%3] and r2 of that iteration = this one's r1 (or z_{k-1})
       const bool pending = !first;
       MinresKdArgs kd = no_kd;
-      kd.do_kd = pending ? 1 : 0; kd.w1 = wn; kd.w2 = w1; kd.w = w2; kd.x = xw;
-      if (enqueue_ka(r2, r1, yb, pending ? V + 2 : V + 0, kd)) return 4;
+      kd.do_kd = pending ? 1 : 0; kd.zold = zn; kd.w1 = wn; kd.w2 = w1; kd.w = w2; kd.x = xw;
+      if (enqueue_ka(src, r1, yb, pending ? V + 2 : V + 0, kd)) return 4;
       if (dist) {                                                // (<v,y>, <x,x>) in one all-reduce
         if (hipeig_allreduce_sum(c, tot, 2)) return 4;
         ++c->mr_collectives;
       }
       MinresRed rc = redC;
       if (dist) rc.tot2 = hipeig_gather_slot(c, A->gl);          // travels with the NEXT exchange
-      hipLaunchKernelGGL(minres_kc_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 1, V + 2, r2, yb, rc, pending ? 1 : 0);
+      hipLaunchKernelGGL(kc_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 1, V + 2, r2, minv, yb, zn, rc, pending ? 1 : 0);
       return 0;
     }
-    if (enqueue_ka(r2, r1, yb, V + 0, no_kd)) return 4;
-    hipLaunchKernelGGL(minres_kc_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 1, V + 2, r2, yb, redC, 0);
-    hipLaunchKernelGGL(minres_kd_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 2, V + 0, r2, w1, w2, wn, xw, redD);
+    if (enqueue_ka(src, r1, yb, V + 0, no_kd)) return 4;
+    hipLaunchKernelGGL(kc_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 1, V + 2, r2, minv, yb, zn, redC, 0);
+    hipLaunchKernelGGL(minres_kd_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 2, V + 0, src, w1, w2, wn, xw, redD);
     return 0;
   };
   // The KD of iteration k as its own kernel (nothing follows to ride on): the end of a chunk on one GPU, the end of the
   // solve on a partitioned run (whose <y,y> shares have not travelled: one extra all-reduce).
   auto enqueue_last_kd = [&](int k) -> int {
     if (!fuse_kd) return 0;
-    MinresArgs al = a;
     if (dist) {
       if (hipeig_allreduce_sum(c, tot + 2, 1)) return 4;
       ++c->mr_collectives;
     }
-    hipLaunchKernelGGL(minres_kd_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, al, V + 2, V + 0, R[k % 3], W[(k + 1) % 3], W[(k + 2) % 3], W[k % 3], xw, redD);
+    hipLaunchKernelGGL(minres_kd_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 2, V + 0, lanczos_src(k), W[(k + 1) % 3], W[(k + 2) % 3], W[k % 3], xw, redD);
     return 0;
   };
   // diagnostic knobs for the rocprofv3-inside-capture question (profiles/r02_hipgraph_under_rocprofv3.txt):
@@ -473,8 +472,8 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
     return 0;
   };
 
-  if (c->use_graph && !dist) {
-    // Single-GPU: a chunk of 18 iterations (a multiple of the rotation period, so every chunk has
+  if (c->use_graph && !dist && !minv) {
+    // Single-GPU, plain solve: a chunk of 18 iterations (a multiple of the rotation period, so every chunk has
     // the same arguments) + the stop check + the copy-back is captured once as a hipGraph and
     // replayed; iterations past maxiter are no-ops (KA's prologue raises istop = 6).  The graph is
     // kept across solves while nothing it has baked in changes.
@@ -486,10 +485,10 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
     memset(&key, 0, sizeof(key));
     key.A = A; key.rowptr = A->d_rowptr; key.col = A->d_col; key.val = A->d_val;
     key.tidx = A->t.idx; key.widx = A->w.idx; key.ws = c->mr_ws; key.state = V; key.parts = c->ytmp;
-    key.n = n; key.nnz = A->nnz; key.variant = variant; key.gA = gA; key.nsweep = nsweepA;
-    key.units = (variant >= 3) ? L.nunits : A->n_row_blocks;
-    key.lds = (int64_t)ldsA;
-    key.csplit = (variant == 4) ? A->w.csplit + (fixed ? 1000 : 0) : 0;
+    key.n = n; key.nnz = A->nnz; key.variant = plan.variant; key.gA = plan.gA; key.nsweep = plan.nsweep;
+    key.units = (plan.variant >= 3) ? plan.tview.nunits : A->n_row_blocks;
+    key.lds = (int64_t)plan.lds;
+    key.csplit = (plan.variant == 4) ? A->w.csplit + (plan.fixed ? 1000 : 0) : 0;
     key.maxiter = maxiter; key.sigma = sigma; key.sign = sign; key.rtol = rtol;
     key.csplit += fuse_kd ? 100000 : 0;
     const int gchunk = 18;
@@ -533,7 +532,14 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
     // no flush at a chunk boundary (it would cost two extra collectives) - the host looks at the record KC left, which
     // holds the tests of the iteration before, and the pending KD is carried into the next chunk; only when the
     // iteration limit is reached are the last KD and the last tests run on their own.
-    const int chunk = dist ? 16 : 32;
+    // Preconditioned solve (15-40 iterations in the benchmark class; tools/precond_bench.py, profiles/r13_jacobi_minres.jsonl):
+    // chunks of 8 / 16 / 32 -> 0.2101 / 0.2106 / 0.2098 ms per iteration at N = 1e6 (19 iterations), 2.174 / 2.166 / 2.169 at
+    // N = 1e7 (18): no difference outside the 0.5 % spread of the repetitions, so the middle value stays.
+    int chunk = dist ? 16 : 32;
+    if (minv) {
+      chunk = 16;
+      if (const char* e = getenv("HIPEIG_PMR_CHUNK")) chunk = atoi(e) > 0 ? atoi(e) : 16;      // tuning knob
+    }
     int k = 0;
     while (k < maxiter) {
       const int kend = (k + chunk < maxiter) ? k + chunk : maxiter;
@@ -562,4 +568,25 @@ extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, doub
     out_stats[4] = h->ynorm; out_stats[5] = h->test1; out_stats[6] = h->test2; out_stats[7] = h->Acond;
   }
   return 0;
+}
+
+extern "C" int hipeig_minres_x0(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign, const double* b, const double* x0,
+                                double* x, double rtol, int maxiter, int* info, double out_stats[8]) {
+  HIPEIG_REQUIRE(c->collectives || A->nrows == A->ncols, "the inner solve needs a square operator (or a row partition)");
+  return minres_solve(c, A, sigma, sign, b, x0, nullptr, x, rtol, maxiter, info, out_stats);
+}
+
+extern "C" int hipeig_minres(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign, const double* b,
+                             double* x, double rtol, int maxiter, int* info, double out_stats[8]) {
+  return hipeig_minres_x0(c, A, sigma, sign, b, nullptr, x, rtol, maxiter, info, out_stats);
+}
+
+// SciPy's minres(A, b, M=...) with M^-1 = diag(minv) (hipeig_jacobi_inverse, minres_precond.hip).
+extern "C" int hipeig_minres_jacobi(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign, const double* b,
+                                    const double* minv, double* x, double rtol, int maxiter, int* info,
+                                    double out_stats[8]) {
+  HIPEIG_REQUIRE(minv != nullptr && ((uintptr_t)minv & 15) == 0, "minv must be a 16-byte aligned device vector");
+  HIPEIG_REQUIRE(!c->collectives, "the preconditioned solve runs on one GPU (whole vectors, no row partition)");
+  HIPEIG_REQUIRE(A->nrows == A->ncols && A->row_offset == 0 && A->col_stride == 0, "the preconditioned solve needs a square operator");
+  return minres_solve(c, A, sigma, sign, b, nullptr, minv, x, rtol, maxiter, info, out_stats);
 }

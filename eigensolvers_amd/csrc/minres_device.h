@@ -103,7 +103,7 @@ static inline void minres_init_state(MinresState* h, double bb) {
 }
 
 // KD's element: w = (v - oldeps*w1 - delta*w2)*denom ; x += phi*w with v = s_old*r2old (with a preconditioner: s_old*z_old,
-// minres_precond.hip).  One definition for the stand-alone kernels and for the epilogue forms, so that all evaluate the
+// minres.hip's PRECOND kernels).  One definition for the stand-alone kernels and for the epilogue forms, so that all evaluate the
 // same expression.
 struct MinresKd {
   double s_old, oldeps, delta, denom, phi;

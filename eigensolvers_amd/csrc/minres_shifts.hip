@@ -17,17 +17,8 @@
 // KA, KC and KU of a step read one, KU's workgroup 0 writes the other.  Once `done` is set every later kernel of a chunk
 // returns at once (KU after copying the final record on), so the result does not depend on how many steps the host enqueues between two looks at the record.
 #include <math.h>
-#include "spmv_device.h"
+#include "sweep_launch.h"
 #include "minres_device.h"
-
-CsrView hipeig_csr_view(const hipeig_csr* A);
-TcooView hipeig_tcoo_view(const hipeig_csr* A, const BlockedLayout& L);
-int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, int fixed, TcooView* last, bool* has_last,
-                          const double** xg, int* ncombine);
-int hipeig_tcoow_reserve(hipeig_ctx* c, const hipeig_csr* A);
-SweepGrid hipeig_sweep_grid(const hipeig_csr* A, int variant);
-int hipeig_csr_pick_variant(hipeig_ctx* c, hipeig_csr* A);
-size_t hipeig_tcoo_lds_bytes(const hipeig_csr* A);
 
 #define MS_MAX_SHIFTS 8
 
@@ -312,23 +303,10 @@ extern "C" int hipeig_minres_shifts(hipeig_ctx* c, hipeig_csr* A, double sign, i
   HIPEIG_CHECK(hipMemcpyAsync(V, h, sizeof(MsState), hipMemcpyHostToDevice, c->stream));
   if (hipeig_sync_checked(c)) return 4;                        // the pinned record is rewritten by the first chunk's copy-back
 
-  int variant = hipeig_csr_pick_variant(c, A);
-  if (variant < 0) return 1;
-  const bool fixed = (variant == 5);
-  if (fixed) variant = 4;
-  if (variant == 4 && hipeig_tcoow_reserve(c, A)) return 1;
-  const CsrView view = hipeig_csr_view(A);
-  const BlockedLayout& L = (variant == 4) ? A->w : A->t;
-  const TcooView tview = hipeig_tcoo_view(A, L);
-  const size_t ldsA = (variant == 4) ? blocked_lds_bytes(A->w, 1) : (variant == 3) ? hipeig_tcoo_lds_bytes(A) : 0;
-  if (variant == 4) {
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)ms_sweep_kernel<4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_TCOOW_LDS_MAX));
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)ms_sweep_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_TCOOW_LDS_MAX));
-  }
-  if (variant == 3)
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)ms_sweep_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_TCOO_LDS_MAX));
-  const SweepGrid sgA = hipeig_sweep_grid(A, variant);
-  const int gA = sgA.wgs, nsweepA = sgA.launches;
+  SweepPlan plan;
+  if (const int rc = sweep_plan_build(c, A, 8, &plan)) return rc;             // combine launch of a column-split sweep: minres.hip's grid
+  if (const int rc = sweep_set_lds_limits(plan, (const void*)ms_sweep_kernel<3>, (const void*)ms_sweep_kernel<4, 0>,
+                                          (const void*)ms_sweep_kernel<4, 1>)) return rc;
   const int gE = grid_wide(n, env_int("HIPEIG_MS_PER_THREAD", 8));         // KC: its reduction finishes in the last workgroup
   // KU: no reduction, so no cap on the grid; every workgroup pays the rotations of its prologue once
   const int64_t upt = env_int("HIPEIG_MS_UPDATE_PER_THREAD", 4);
@@ -336,10 +314,7 @@ extern "C" int hipeig_minres_shifts(hipeig_ctx* c, hipeig_csr* A, double sign, i
   if (gU64 < 1) gU64 = 1;
   if (gU64 > ((int64_t)1 << 22)) gU64 = (int64_t)1 << 22;
   const int gU = (int)gU64;
-  const bool split = (variant == 4) && A->w.csplit > 1;
-  const int gC = grid_wide(n, 8);                              // combine launch of a column-split sweep (minres.hip)
-  const int nPA = split ? gC : gA * nsweepA;
-  HIPEIG_REQUIRE(nPA <= HIPEIG_WIDE_PARTIALS, "too many sweeps for the partial-sum buffer");
+  const int nPA = plan.nPA;
   double* pA = c->d_partials;
   double* pC = c->d_partials + HIPEIG_WIDE_PARTIALS;
   double* tot = c->d_scalars + SC_MINRES_TOT;                           // [0] <v,w>, [1] <w,w>
@@ -358,44 +333,12 @@ extern "C" int hipeig_minres_shifts(hipeig_ctx* c, hipeig_csr* A, double sign, i
   ua.probe = probe ? 1 : 0;
 
   auto enqueue_sweep = [&](const MsState* Sin, double* rk, double* rkm1, double* w) -> int {
-    const double* xg = nullptr;
-    TcooView tv = tview;
-#define MS_LAUNCH(VAR, FIX, GRID, THREADS, LDS, TV, OFF)                                                              \
-    do {                                                                                                              \
-      const MinresRed ra{pA + (OFF), pA, nPA, (unsigned)nPA, cntA, tot + 0, nullptr};                                 \
-      hipLaunchKernelGGL((ms_sweep_kernel<VAR, FIX>), dim3(GRID), dim3(THREADS), LDS, c->stream, view, TV, xg, Sin, rk, rkm1, w, ra); \
-    } while (0)
-    if (variant == 4) {
-      bool has_last = true;
-      int ncombine = 0;
-      if (hipeig_tcoow_run_plan(c, A, rk, fixed ? 1 : 0, &tv, &has_last, &xg, &ncombine)) return 4;
-      if (has_last) {
-        for (int sw = 0; sw < nsweepA; ++sw) {
-          tv.unit_begin = sw * gA;
-          if (fixed) MS_LAUNCH(4, 1, gA, TCOOW_THREADS, ldsA, tv, sw * gA);
-          else MS_LAUNCH(4, 0, gA, TCOOW_THREADS, ldsA, tv, sw * gA);
-        }
-      }
-      if (ncombine) {
-        TcooView tc = tv;
-        tc.raw_out = c->ytmp;
-        tc.part_base = ncombine;                               // number of slabs to add
-        MS_LAUNCH(5, 0, gC, HIPEIG_BLOCK, 0, tc, 0);
-      }
-      return 0;
-    }
-    if (hipeig_allgather_x(c, A->gl, rk, n, &xg)) return 4;   // no communicator: the operand itself
-    if (variant == 3) {
-      for (int sw = 0; sw < nsweepA; ++sw) {
-        tv.unit_begin = sw * gA * 4;
-        MS_LAUNCH(3, 0, gA, HIPEIG_BLOCK, ldsA, tv, sw * gA);
-      }
-    } else if (variant == 1) {
-      MS_LAUNCH(1, 0, gA, HIPEIG_BLOCK, 0, tview, 0);
-    } else {
-      MS_LAUNCH(2, 0, gA, HIPEIG_BLOCK, 0, tview, 0);
-    }
-#undef MS_LAUNCH
+    SweepOperand op;
+    if (sweep_prepare(c, A, plan, rk, &op)) return 4;         // no communicator: the operand itself
+    sweep_launch(c, plan, op, [&](auto v, auto f, int grid, int threads, size_t lds, const TcooView& tv, const double* xg, int off) {
+      const MinresRed ra{pA + off, pA, nPA, (unsigned)nPA, cntA, tot + 0, nullptr};
+      hipLaunchKernelGGL((ms_sweep_kernel<decltype(v)::value, decltype(f)::value>), dim3(grid), dim3(threads), lds, c->stream, plan.view, tv, xg, Sin, rk, rkm1, w, ra);
+    });
     return 0;
   };
 

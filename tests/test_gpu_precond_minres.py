@@ -1,4 +1,4 @@
-"""The Jacobi-preconditioned device MINRES (``linearSystemArgs["preconditioner"] = "jacobi"``, csrc/minres_precond.hip)
+"""The Jacobi-preconditioned device MINRES (``linearSystemArgs["preconditioner"] = "jacobi"``, csrc/minres.hip, csrc/minres_precond.hip)
 against its NumPy twin, which ``test_precond_minres_cpu.py`` pins to ``scipy.sparse.linalg.minres(A, b, M=...)``.
 
 Tolerances are those of ``test_gpu_parity.py::test_minres_tracks_the_oracle`` with the twin in the oracle's place:
@@ -212,6 +212,89 @@ def test_chunk_independence(hip, gapped16, monkeypatch):
     for x, itn, istop in out[1:]:
         assert (itn, istop) == out[0][1:]
         np.testing.assert_array_equal(x, out[0][0])
+
+
+# ---------------------------------------------------------------- one workspace for the plain and the preconditioned solve
+_SHIFTS = [0.02 + 0.1j, 0.3 + 0.1j, -0.2 + 0.05j]
+
+
+def _workspace_calls(hip, ctx):
+    """The solves that share the context's MINRES workspace, each as a function of nothing returning its arrays: a plain
+    solve (7 vectors of 4000), a Jacobi solve (9 of 4001: the buffer grows and moves), a three-shift solve (which borrows the
+    partial-sum areas and totals of both)."""
+    Hh, b = gapped_csr_host(4000, 16, seed=7), pc.unit_guess(4000)
+    Hx, bx = pc.exact_hit_operator()[0], pc.unit_guess(4001)
+    H = hip.HipCsrOperator.from_scipy(Hh, ctx=ctx)
+    X = hip.HipCsrOperator.from_scipy(Hx, ctx=ctx)
+    so = {"linearSystemArgs": {"linearSolver": "minres_shifted", "linearIter": 2000, "linear_tol": 1e-8, "linear_atol": 0.0}}
+    return {
+        "plain": lambda: [hip.HipVector.solve(H, hip.HipVector(b.copy(), _opts(2000, 1e-10, pre=None), ctx=ctx), pc.SIGMA).array],
+        "jacobi": lambda: [hip.HipVector.solve(X, hip.HipVector(bx.copy(), _opts(2000, 1e-10), ctx=ctx), pc.SIGMA).array],
+        "shifted": lambda: [x.array for x in hip.HipVector._solve_shifts(H, hip.HipVector(b.copy(), so, ctx=ctx), _SHIFTS)],
+    }
+
+
+@pytest.fixture(scope="module")
+def workspace_refs(hip):
+    """Every call of ``_workspace_calls`` made first on a fresh context of its own."""
+    return {name: _workspace_calls(hip, hip.HipContext(0))[name]() for name in ("plain", "jacobi", "shifted")}
+
+
+@pytest.mark.parametrize("fresh", [False, True])
+def test_shared_workspace_plain_launches(hip, workspace_refs, fresh):
+    """Plain -> Jacobi -> plain -> shifted -> Jacobi on ONE context gives, call by call, the bits of the same call made
+    first on a fresh context: on the default context (whatever ran there before) and on a new one, where the Jacobi solve
+    grows the workspace from 7 x 4000 to 9 x 4032 doubles under the plain solve's feet."""
+    calls = _workspace_calls(hip, hip.HipContext(0) if fresh else hip.HipContext.default())
+    for name in ("plain", "jacobi", "plain", "shifted", "jacobi"):
+        got = calls[name]()
+        assert len(got) == len(workspace_refs[name])
+        for g, r in zip(got, workspace_refs[name]):
+            assert np.isfinite(g).all() and np.abs(g).max() > 0
+            np.testing.assert_array_equal(g, r)
+
+
+def _slack_solves(hip, ctx):
+    """A plain solve at n = 4100 and two larger solves (n = 5000) that would fit in the slack a 9-vector workspace of 4001
+    leaves a 7-vector solve: an ``x0`` that is the exact solution, which returns before any iteration, and a whole solve."""
+    Ha, ba = gapped_csr_host(4100, 16, seed=7), pc.unit_guess(4100)
+    Hb, bb = gapped_csr_host(5000, 16, seed=7), pc.unit_guess(5000)
+    A = hip.HipCsrOperator.from_scipy(Ha, ctx=ctx)
+    B = hip.HipCsrOperator.from_scipy(Hb, ctx=ctx)
+    D = hip.HipCsrOperator.from_scipy(sp.identity(5000, format="csr") * 2.0, ctx=ctx)
+    o = _opts(2000, 1e-10, pre=None)
+
+    def exact_guess():                                          # (0 I - 2 I) x = -2 x0 with x0 given: r1 = b - A x0 = 0 exactly
+        W = hip.HipVector.solve(D, hip.HipVector(-2.0 * bb, o, ctx=ctx), 0.0, x0=hip.HipVector(bb.copy(), ctx=ctx))
+        assert W.last_solve_stats["iterations"] == 0
+        np.testing.assert_array_equal(W.array, bb)
+
+    return {"small": lambda: hip.HipVector.solve(A, hip.HipVector(ba.copy(), o, ctx=ctx), pc.SIGMA).array,
+            "large": lambda: hip.HipVector.solve(B, hip.HipVector(bb.copy(), o, ctx=ctx), pc.SIGMA).array,
+            "exact_guess": exact_guess}
+
+
+def test_shared_workspace_under_graph_replay(hip, workspace_refs, monkeypatch):
+    """HIPEIG_GRAPH=1 (read when a context is created): the plain solve's captured chunk has the workspace pointer and the
+    vectors' stride baked in, and the Jacobi solve in between moves that workspace.  The replay after the move must give
+    the bits of the replay before it and of the plain launches; the Jacobi solve never replays and gives its plain-launch
+    bits.  Then larger solves that fit in the slack of the 9-vector buffer run between two replays of a smaller one - one
+    of them leaves before it captures anything - and the smaller solve must still give its plain-launch bits."""
+    plain = _slack_solves(hip, hip.HipContext(0))
+    ref_small, ref_large = plain["small"](), plain["large"]()
+    monkeypatch.setenv("HIPEIG_GRAPH", "1")
+    ctx = hip.HipContext(0)
+    calls = _workspace_calls(hip, ctx)
+    first, jac, second = calls["plain"](), calls["jacobi"](), calls["plain"]()
+    np.testing.assert_array_equal(second[0], first[0])
+    np.testing.assert_array_equal(second[0], workspace_refs["plain"][0])
+    np.testing.assert_array_equal(jac[0], workspace_refs["jacobi"][0])
+    slack = _slack_solves(hip, ctx)
+    np.testing.assert_array_equal(slack["small"](), ref_small)
+    slack["exact_guess"]()
+    np.testing.assert_array_equal(slack["small"](), ref_small)
+    np.testing.assert_array_equal(slack["large"](), ref_large)
+    np.testing.assert_array_equal(slack["small"](), ref_small)
 
 
 # ---------------------------------------------------------------- refusals
