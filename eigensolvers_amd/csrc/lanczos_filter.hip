@@ -25,13 +25,7 @@
 // "fp32 basis" below.
 #include <limits.h>
 #include <math.h>
-#include "spmm_device.h"
-
-int hipeig_block_pick_variant(hipeig_ctx* c, hipeig_csr* A, int K, int for_solve);
-BcooView hipeig_bcoo_view(const hipeig_csr* A, const BlockedLayout& L);
-int hipeig_block_pack(hipeig_ctx* c, int K, int64_t n, int k, const double* const* cols, double* blk);
-int hipeig_block_unpack(hipeig_ctx* c, int K, int64_t n, int k, const double* blk, double* const* cols);
-int hipeig_rowowner_grid(const hipeig_ctx* c, const hipeig_csr* A);
+#include "block_sweep_launch.h"
 
 #define LF_MAX_SHIFTS 32
 #define LF_HEAD_DOUBLES 4096                                  // doubles kept for the state record
@@ -106,24 +100,6 @@ lf_sweep_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t* _
   if (threadIdx.x < K) partials[(size_t)blockIdx.x * K + threadIdx.x] = tot;
 }
 
-// Fold (a0, a1) - partials of columns 2(t % (K/2)) and the next - over the workgroup; record in threads 0..K-1.
-template <int K>
-__device__ __forceinline__ void lf_reduce_pairs(double a0, double a1, double* lds, double* __restrict__ out_record) {
-#pragma unroll
-  for (int off = K / 2; off < 64; off <<= 1) {
-    a0 += __shfl_xor(a0, off, 64);
-    a1 += __shfl_xor(a1, off, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane < K / 2) { lds[wid * K + lane * 2] = a0; lds[wid * K + lane * 2 + 1] = a1; }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double r = lds[threadIdx.x];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += lds[w * K + threadIdx.x];
-    out_record[threadIdx.x] = r;
-  }
-}
-
 // W -= (alpha / beta_k) R_k per column, and the partials of <w, w>.  S32: the finished w also goes, rounded to fp32
 // (round to nearest even), to w32 - a slot of an fp32 basis - in one 8-byte store of the thread's column pair.
 template <int K, bool S32 = false>
@@ -155,7 +131,7 @@ lf_kc_kernel(int64_t n, const LfState* __restrict__ S, const double* __restrict_
     if (S32) reinterpret_cast<float2*>(w32)[t] = make_float2((float)wv.x, (float)wv.y);
     a0 = fma(wv.x, wv.x, a0); a1 = fma(wv.y, wv.y, a1);
   }
-  lf_reduce_pairs<K>(a0, a1, red, partials + (size_t)blockIdx.x * K);
+  block_reduce_pairs<K>(a0, a1, red, partials + (size_t)blockIdx.x * K);
 }
 
 // The packed b, slot 0 of an fp32 basis, rounded once: a column pair per thread, as above.
@@ -530,21 +506,14 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   HIPEIG_CHECK(hipMemcpyAsync(V, h, sizeof(LfState), hipMemcpyHostToDevice, c->stream));
   if (hipeig_sync_checked(c)) return 4;                       // the pinned record is rewritten by the first copy-back
 
-  const int bv = hipeig_block_pick_variant(c, A, K, 1);
-  if (bv < 0) return 1;
-  const BlockedLayout& L = A->b[layout_slot(K)];
-  const BcooView tview = hipeig_bcoo_view(A, L);
-  if (bv == 2)
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)lf_sweep_kernel<2, K>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)HIPEIG_BCOO_LDS_MAX));
-  const SweepGrid sg = (bv == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
-  const int gA = sg.wgs, nsweepA = sg.launches;
-  const int nPA = gA * nsweepA;
-  HIPEIG_REQUIRE(nPA <= HIPEIG_MAX_PARTIALS, "too many sweeps for the partial-sum buffer");
+  BlockSweepPlan plan;
+  if (const int rc = block_sweep_plan_build<K>(c, A, 1, &plan)) return rc;
+  if (const int rc = block_sweep_set_lds_limit(plan, lf_sweep_kernel<2, K>)) return rc;
+  const int nPA = plan.nPA;
   const int gE = grid_for(n * (K / 2), lf_env_int("HIPEIG_LF_PER_THREAD", 32));
   double* pA = c->d_partials;
-  double* pC = c->d_partials + (size_t)HIPEIG_MAX_PARTIALS * BCOO_KMAX;
-  HIPEIG_REQUIRE(c->partials_doubles >= (size_t)2 * HIPEIG_MAX_PARTIALS * BCOO_KMAX, "partial-sum workspace too small");
+  double* pC = c->d_partials + BLOCK_PART_STRIDE;
+  HIPEIG_REQUIRE(c->partials_doubles >= (size_t)2 * BLOCK_PART_STRIDE, "partial-sum workspace too small");
 
   LfShifts sh;
   memset(&sh, 0, sizeof(sh));
@@ -552,17 +521,10 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
   for (int q = 0; q < nshift; ++q) { sh.zr[q] = zr[q]; sh.zi[q] = zi[q]; }
 
   auto enqueue_sweep = [&](const double* rk, const double* rkm1, double* w) {
-    if (bv == 2) {
-      BcooView tv = tview;
-      for (int sw = 0; sw < nsweepA; ++sw) {
-        tv.unit_begin = sw * gA;
-        hipLaunchKernelGGL((lf_sweep_kernel<2, K>), dim3(gA), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream, tv,
-                           A->d_rowptr, A->d_col, A->d_val, n, (const LfState*)V, rk, rkm1, w, pA + (size_t)sw * gA * K);
-      }
-    } else {
-      hipLaunchKernelGGL((lf_sweep_kernel<1, K>), dim3(gA), dim3(HIPEIG_BLOCK), 0, c->stream, tview, A->d_rowptr, A->d_col,
-                         A->d_val, n, (const LfState*)V, rk, rkm1, w, pA);
-    }
+    block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int off) {
+      hipLaunchKernelGGL((lf_sweep_kernel<decltype(v)::value, K>), dim3(grid), dim3(threads), lds, c->stream, tv, A->d_rowptr,
+                         A->d_col, A->d_val, n, (const LfState*)V, rk, rkm1, w, pA + (size_t)off * K);
+    });
   };
 
   int steps = 0;
@@ -699,29 +661,17 @@ template <int K, int NC>
 static int lf_enqueue_products(hipeig_ctx* c, hipeig_csr* A, const double* d_tab, const int* d_m, int first, int mmax,
                                double* const* Vb, double* Q, int64_t nb) {
   const int64_t n = A->nrows;
-  const int bv = hipeig_block_pick_variant(c, A, K, 1);
-  if (bv < 0) return 1;
-  const BlockedLayout& L = A->b[layout_slot(K)];
-  const BcooView tview = hipeig_bcoo_view(A, L);
-  if (bv == 2)
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)lf_combine_kernel<2, K, NC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)HIPEIG_BCOO_LDS_MAX));
-  const SweepGrid sg = (bv == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
+  BlockSweepPlan plan;
+  if (const int rc = block_sweep_plan_build<K>(c, A, 1, &plan)) return rc;
+  if (const int rc = block_sweep_set_lds_limit(plan, lf_combine_kernel<2, K, NC>)) return rc;
   for (int i = first; i + 1 < mmax; ++i) {
     const double* tab = d_tab + (int64_t)(i - first) * LF_TAB(K, NC);
     const double* rk = Vb[i & 1];
     double* rkm1 = Vb[(i + 1) & 1];
-    if (bv == 2) {
-      BcooView tv = tview;
-      for (int sw = 0; sw < sg.launches; ++sw) {
-        tv.unit_begin = sw * sg.wgs;
-        hipLaunchKernelGGL((lf_combine_kernel<2, K, NC>), dim3(sg.wgs), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream,
-                           tv, A->d_rowptr, A->d_col, A->d_val, n, tab, d_m, i, rk, rkm1, Q, nb);
-      }
-    } else {
-      hipLaunchKernelGGL((lf_combine_kernel<1, K, NC>), dim3(sg.wgs), dim3(HIPEIG_BLOCK), 0, c->stream, tview, A->d_rowptr,
-                         A->d_col, A->d_val, n, tab, d_m, i, rk, rkm1, Q, nb);
-    }
+    block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int) {      // no partials
+      hipLaunchKernelGGL((lf_combine_kernel<decltype(v)::value, K, NC>), dim3(grid), dim3(threads), lds, c->stream, tv,
+                         A->d_rowptr, A->d_col, A->d_val, n, tab, d_m, i, rk, rkm1, Q, nb);
+    });
   }
   hipLaunchKernelGGL((lf_last_term_kernel<K, NC>), dim3(grid_stream(n * K)), dim3(HIPEIG_BLOCK), 0, c->stream, n,
                      d_tab + (int64_t)(mmax - 1 - first) * LF_TAB(K, NC), d_m, mmax - 1, (const double*)Vb[(mmax - 1) & 1], Q,

@@ -13,18 +13,7 @@
 //   KC  Y -= (alfa/beta) R2                                               + partials <y_j, y_j>
 //   KD  W = (V - oldeps W1 - delta W2)/gamma ; X += phi W                  + partials <x_j, x_j>
 #include "minres_device.h"
-#include "spmm_device.h"
-
-int hipeig_block_pick_variant(hipeig_ctx* c, hipeig_csr* A, int K, int for_solve);
-BcooView hipeig_bcoo_view(const hipeig_csr* A, const BlockedLayout& L);
-int hipeig_block_allgather(hipeig_ctx* c, hipeig_csr* A, int K, const double* xb_local, const double** xb_full);
-int hipeig_block_pack(hipeig_ctx* c, int K, int64_t n, int k, const double* const* cols, double* blk);
-int hipeig_block_unpack(hipeig_ctx* c, int K, int64_t n, int k, const double* blk, double* const* cols);
-int hipeig_rowowner_grid(const hipeig_ctx* c, const hipeig_csr* A);
-double* hipeig_gather_block_slot(hipeig_ctx* c, const GatherLayout& gl, int K);
-int hipeig_block_reserve(hipeig_ctx* c, const GatherLayout& gl, int K);
-
-#define MRB_PART_STRIDE (HIPEIG_MAX_PARTIALS * BCOO_KMAX)     // doubles between the three partial areas
+#include "block_sweep_launch.h"
 
 // Per-operand sum of `count` partial records for the operand threadIdx.x % K (count == 1: the record
 // has already been reduced, e.g. by an all-reduce).
@@ -89,24 +78,6 @@ minres_block_ka_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int
   else csr_rowowner_block_sweep<K>(rowptr, col, val, nrows, xg, epi, acc);
   const double tot = block_reduce_cols<K>(acc, red);
   if (threadIdx.x < K) partials[(size_t)blockIdx.x * K + threadIdx.x] = tot;
-}
-
-// Fold (a0, a1) - partials of operands 2(t % (K/2)) and the next - over the workgroup; record in threads 0..K-1.
-template <int K>
-__device__ __forceinline__ void block_reduce_pairs(double a0, double a1, double* lds, double* __restrict__ out_record) {
-#pragma unroll
-  for (int off = K / 2; off < 64; off <<= 1) {
-    a0 += __shfl_xor(a0, off, 64);
-    a1 += __shfl_xor(a1, off, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane < K / 2) { lds[wid * K + lane * 2] = a0; lds[wid * K + lane * 2 + 1] = a1; }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double r = lds[threadIdx.x];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += lds[w * K + threadIdx.x];
-    out_record[threadIdx.x] = r;
-  }
 }
 
 template <int K>
@@ -286,16 +257,9 @@ static int minres_block_impl(hipeig_ctx* c, hipeig_csr* A, double sigma, double 
   HIPEIG_CHECK(hipMemcpyAsync(V, h, K * sizeof(MinresState), hipMemcpyHostToDevice, c->stream));
   if (hipeig_sync_checked(c)) return 4;       // the pinned records are rewritten by the first copy-back
 
-  const int bv = hipeig_block_pick_variant(c, A, K, 1);
-  if (bv < 0) return 1;
-  const BlockedLayout& L = A->b[layout_slot(K)];
-  const BcooView tview = hipeig_bcoo_view(A, L);
-  if (bv == 2)
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_block_ka_kernel<2, K>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)HIPEIG_BCOO_LDS_MAX));
-  const SweepGrid sg = (bv == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
-  const int gA = sg.wgs, nsweepA = sg.launches;
-  HIPEIG_REQUIRE((int64_t)nsweepA * gA <= HIPEIG_MAX_PARTIALS, "too many sweeps for the partial-sum buffer");
+  BlockSweepPlan plan;
+  if (const int rc = block_sweep_plan_build<K>(c, A, 1, &plan)) return rc;
+  if (const int rc = block_sweep_set_lds_limit(plan, minres_block_ka_kernel<2, K>, minres_block_ka_kernel<2, K, 1>)) return rc;
   // element-wise kernels: every workgroup sums the previous kernel's gE x K partials in its prologue, so FEWER, fatter
   // workgroups pay twice (less prologue traffic, fewer partials).  Measured (tools/experiments/mrb_grid_sweep.sh, N = 1e6,
   // K = 8, ms per block iteration): 4 / 8 / 16 / 32 / 64 items per thread -> 0.483 / 0.483 / 0.469 / 0.463 / 0.496.
@@ -303,16 +267,16 @@ static int minres_block_impl(hipeig_ctx* c, hipeig_csr* A, double sigma, double 
   if (const char* e = getenv("HIPEIG_MRB_PER_THREAD")) per_thread = atoi(e) > 0 ? atoi(e) : 32;
   const int gE = grid_for(n * (K / 2), per_thread);
   double* pA = c->d_partials;
-  double* pC = c->d_partials + MRB_PART_STRIDE;
-  double* pD = c->d_partials + 2 * MRB_PART_STRIDE;
-  HIPEIG_REQUIRE(c->partials_doubles >= (size_t)3 * MRB_PART_STRIDE, "partial-sum workspace too small");
+  double* pC = c->d_partials + BLOCK_PART_STRIDE;
+  double* pD = c->d_partials + 2 * BLOCK_PART_STRIDE;
+  HIPEIG_REQUIRE(c->partials_doubles >= (size_t)3 * BLOCK_PART_STRIDE, "partial-sum workspace too small");
   const bool dist = c->collectives != 0;
   // row-partitioned run: reduced records of 8 - [0..7] <v,y>, [8..15] <x,x> (ONE all-reduce), [16..23] / [24..31] the
   // end-of-solve flush
   double* red = c->d_scalars + SC_COMM;
   MinresArgs a;
   a.sigma = sigma; a.sign = sign; a.rtol = rtol; a.maxiter = maxiter; a.sC = 0;
-  const int nPA = gA * nsweepA;
+  const int nPA = plan.nPA;                              // records of <v_j,y_j> partials one sweep leaves in pA
   a.pA = dist ? red + 0 : pA; a.nA = dist ? 1 : nPA;
   a.pC = pC; a.nC = gE;
   a.pD = dist ? red + 8 : pD; a.nD = dist ? 1 : gE;
@@ -328,32 +292,18 @@ static int minres_block_impl(hipeig_ctx* c, hipeig_csr* A, double sigma, double 
   c->mr_collectives = 0;
 
   auto launch_ka = [&](const double* xg, double* r2, double* r1, double* yb, bool late) {
-    if (bv == 2) {
-      BcooView tv = tview;
-      for (int sw = 0; sw < nsweepA; ++sw) {
-        tv.unit_begin = sw * gA;
-        if (late) hipLaunchKernelGGL((minres_block_ka_kernel<2, K, 1>), dim3(gA), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream,
-                                     tv, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)sw * gA * K);
-        else hipLaunchKernelGGL((minres_block_ka_kernel<2, K>), dim3(gA), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream,
-                                tv, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)sw * gA * K);
-      }
-    } else if (late) {
-      hipLaunchKernelGGL((minres_block_ka_kernel<1, K, 1>), dim3(gA), dim3(HIPEIG_BLOCK), 0, c->stream,
-                         tview, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA);
-    } else {
-      hipLaunchKernelGGL((minres_block_ka_kernel<1, K>), dim3(gA), dim3(HIPEIG_BLOCK), 0, c->stream,
-                         tview, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA);
-    }
+    block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int off) {
+      if (late) hipLaunchKernelGGL((minres_block_ka_kernel<decltype(v)::value, K, 1>), dim3(grid), dim3(threads), lds, c->stream,
+                                   tv, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)off * K);
+      else hipLaunchKernelGGL((minres_block_ka_kernel<decltype(v)::value, K>), dim3(grid), dim3(threads), lds, c->stream,
+                              tv, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)off * K);
+    });
   };
   // KD of iteration `it` (buffers of that iteration)
   auto launch_kd = [&](int it, const MinresArgs& ak) {
     hipLaunchKernelGGL(minres_block_kd_kernel<K>, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, ak, V + 16, V + 0,
                        R[it % 3], W[(it + 1) % 3], W[(it + 2) % 3], W[it % 3], xw, pD);
   };
-
-  if (bv == 2)
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)minres_block_ka_kernel<2, K, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)HIPEIG_BCOO_LDS_MAX));
 
   auto enqueue_iteration = [&](int it) -> int {
     double* r2 = R[it % 3];

@@ -2,7 +2,7 @@
 // product Y = H X (hipeig_spmm).  Kernel bodies live in spmm_device.h; the lock-step block MINRES
 // (minres_block.hip) fuses its vector updates into the same sweeps.
 #include <vector>
-#include "spmm_device.h"
+#include "block_sweep_launch.h"
 
 struct PtrTable8 { const double* p[BCOO_KPACK]; };
 struct OutTable8 { double* p[BCOO_KPACK]; };
@@ -256,23 +256,18 @@ int hipeig_rowowner_grid(const hipeig_ctx* c, const hipeig_csr* A) {
 template <int K, class Epi>
 static int spmm_block_run(hipeig_ctx* c, hipeig_csr* A, const double* Xb, const Epi& epi) {
   if (A->nrows == 0) return 0;
-  const int bv = hipeig_block_pick_variant(c, A, K, 0);
-  if (bv < 0) return 1;
+  BlockSweepPlan plan;
+  if (const int rc = block_sweep_plan_build<K>(c, A, 0, &plan)) return rc;
   const double* xg = nullptr;
   if (hipeig_block_allgather(c, A, K, Xb, &xg)) return 4;
-  if (bv == 2) {
-    HIPEIG_CHECK(hipFuncSetAttribute((const void*)spmm_bcoo_kernel<K, Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIPEIG_BCOO_LDS_MAX));
-    const BlockedLayout& L = A->b[layout_slot(K)];
-    BcooView t = hipeig_bcoo_view(A, L);
-    const SweepGrid g = blocked_grid(L);
-    for (int i = 0; i < g.launches; ++i) {                    // one launch per sweep of the windows
-      t.unit_begin = i * g.wgs;
-      hipLaunchKernelGGL((spmm_bcoo_kernel<K, Epi>), dim3(g.wgs), dim3(BCOO_THREADS), blocked_lds_bytes(L, K), c->stream, t, xg, epi);
-    }
-  } else {
-    hipLaunchKernelGGL((spmm_rowowner_kernel<K, Epi>), dim3(hipeig_rowowner_grid(c, A)), dim3(HIPEIG_BLOCK), 0, c->stream,
-                       A->d_rowptr, A->d_col, A->d_val, A->nrows, xg, epi);
-  }
+  if (const int rc = block_sweep_set_lds_limit(plan, spmm_bcoo_kernel<K, Epi>)) return rc;
+  block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int) {
+    if constexpr (decltype(v)::value == 2)
+      hipLaunchKernelGGL((spmm_bcoo_kernel<K, Epi>), dim3(grid), dim3(threads), lds, c->stream, tv, xg, epi);
+    else
+      hipLaunchKernelGGL((spmm_rowowner_kernel<K, Epi>), dim3(grid), dim3(threads), lds, c->stream,
+                         A->d_rowptr, A->d_col, A->d_val, A->nrows, xg, epi);
+  });
   HIPEIG_CHECK(hipGetLastError());
   return 0;
 }

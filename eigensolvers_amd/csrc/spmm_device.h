@@ -230,6 +230,24 @@ __device__ __forceinline__ double block_reduce_cols(double v, double* lds) {
   return r;
 }
 
+// Fold (a0, a1) - partials of operands 2(t % (K/2)) and the next - over the workgroup; record in threads 0..K-1.
+template <int K>
+__device__ __forceinline__ void block_reduce_pairs(double a0, double a1, double* lds, double* __restrict__ out_record) {
+#pragma unroll
+  for (int off = K / 2; off < 64; off <<= 1) {
+    a0 += __shfl_xor(a0, off, 64);
+    a1 += __shfl_xor(a1, off, 64);
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane < K / 2) { lds[wid * K + lane * 2] = a0; lds[wid * K + lane * 2 + 1] = a1; }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    double r = lds[threadIdx.x];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += lds[w * K + threadIdx.x];
+    out_record[threadIdx.x] = r;
+  }
+}
+
 // Every thread obtains the fixed-order sum of the partials of ITS operand (threadIdx.x % K):
 // p holds count records of K doubles.  lds must hold (blockDim/64)*K doubles.
 template <int K>

@@ -4,7 +4,8 @@
 //   SweepPlan plan;  sweep_plan_build(c, A, rows_per_thread, &plan);  sweep_set_lds_limits(plan, k<3>, k<4,0>, k<4,1>);
 //   per sweep:  sweep_prepare(...)  (exchange, waits, raw launches; hands back the gathered operand)
 //               sweep_launch(...)   (the epilogue launches, then the combine launch of a column-split sweep)
-// hipeig_spmv's launch_spmv (spmv.hip) launches reduction-free kernels of its own and does not come through here.
+// hipeig_spmv's launch_spmv (spmv.hip) launches reduction-free kernels of its own and does not come through here; the
+// sweeps of interleaved blocks have their own launcher, block_sweep_launch.h.
 #pragma once
 #include <type_traits>
 #include "spmv_device.h"

@@ -14,25 +14,12 @@ import pytest
 import scipy.linalg as la
 import scipy.sparse as sp
 
+from _block_cases import block_solve as _block_solve, check_block_solve, opts as _opts, within as _within
 from conftest import load_golden
 from eigensolvers_amd import _lib
 from eigensolvers_amd.generators import gapped_csr_host
-from oracle.minres_ref import minres as minres_ref
 
 pytestmark = pytest.mark.gpu
-
-
-def _within(got, ref, bound):
-    got, ref, bound = np.asarray(got), np.asarray(ref), np.asarray(bound)
-    err = np.abs(got - ref)
-    bad = ~(err <= bound)
-    assert not bad.any(), f"max excess {np.max(err - bound):.3e} at {int(np.argmax(err - bound))}, {int(bad.sum())} elements"
-
-
-def _opts(it=2000, tol=1e-10, **extra):
-    d = {"linearSystemArgs": {"linearSolver": "minres", "linearIter": it, "linear_tol": tol}}
-    d.update(extra)
-    return d
 
 
 @pytest.mark.parametrize("block_variant", [1, 2])
@@ -93,12 +80,6 @@ def test_block_product_ragged_empty_and_dense_rows(hip, block_variant, monkeypat
         _within(hip.HipVector(Ys[j]).array, ref[100:900, j], bound[100:900, j])
 
 
-def _block_solve(hip, H, B, sigma, it, tol, reverse=False):
-    vecs = [hip.HipVector(B[:, j].copy(), _opts(it, tol)) for j in range(B.shape[1])]
-    out = hip.HipVector.solveBlock(H, vecs, sigma, reverseGF=reverse)
-    return out, vecs
-
-
 @pytest.mark.parametrize("block_variant", [1, 2])
 @pytest.mark.parametrize("k,rtol", [(8, 1e-10), (3, 1e-6), (4, 1e-8), (5, 1e-4), (11, 1e-8)])
 def test_block_minres_equals_the_single_solves(hip, gapped4000, block_variant, k, rtol):
@@ -119,22 +100,7 @@ def test_block_minres_equals_the_single_solves(hip, gapped4000, block_variant, k
         B[:, 5] = 0.0                                                                    # beta1 = 0: x = 0, no iterations
         B[:, 6] *= 1e-7                                                                  # scaling must not matter
     X, vecs = _block_solve(hip, H, B, 0.02, 2000, rtol)
-    assert len(X) == k
-    for j in range(k):
-        st = X[j].last_solve_stats
-        if not np.any(B[:, j]):
-            assert st["iterations"] == 0 and np.all(X[j].array == 0.0)
-            continue
-        xo, info, itn, istop = minres_ref(lambda v: 0.02 * v - Hh @ v, B[:, j], rtol=rtol, maxiter=2000)
-        single = hip.HipVector.solve(H, hip.HipVector(B[:, j].copy(), _opts(2000, rtol)), 0.02)
-        ss = single.last_solve_stats
-        assert (st["iterations"], st["istop"]) == (ss["iterations"], ss["istop"]), f"column {j}"
-        assert (st["iterations"], st["istop"]) == (itn, istop), f"column {j} vs oracle"
-        xtol = max(1e-9, 100 * rtol) * np.linalg.norm(xo)
-        _within(X[j].array, xo, xtol)
-        _within(X[j].array, single.array, xtol)
-        assert abs(st["rnorm"] - ss["rnorm"]) <= 0.05 * ss["rnorm"] + 1e-300      # the estimate moves with the summation order
-        assert vecs[j].last_solve_stats is st
+    check_block_solve(hip, H, Hh, B, X, vecs, rtol)
     if k == 8:
         its = [X[j].last_solve_stats["iterations"] for j in range(k)]
         assert its[2] < min(its[0], its[1]) and its[5] == 0               # columns really stopped at different times
