@@ -31,7 +31,6 @@
 #include "sweep_launch.h"
 #include "minres_device.h"
 
-void hipeig_phase_mark(hipeig_ctx* c, int k);
 // minres_precond.hip: r2 = b, z = minv (.) b and *bz = <b, z> (synchronises; refuses <b, z> < 0)
 int hipeig_pmr_start(hipeig_ctx* c, int64_t n, const double* b, const double* minv, double* r2, double* z, int grid,
                      const MinresRed& rc, double* bz);
@@ -365,7 +364,8 @@ static int minres_solve(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign,
   int ct = 8;
   if (const char* e = getenv("HIPEIG_MR_COMBINE_PER_THREAD")) ct = atoi(e) > 0 ? atoi(e) : 8;   // tuning knob
   SweepPlan plan;
-  if (const int rc = sweep_plan_build(c, A, ct, &plan)) return rc;
+  if (const int rc = sweep_plan_build(c, A, grid_wide(n, ct), &plan)) return rc;
+  HIPEIG_REQUIRE(plan.nPA <= HIPEIG_WIDE_PARTIALS, "too many sweeps for the partial-sum buffer");
   // column splits serve the slabs of row-partitioned runs, which the preconditioned solve does not take
   HIPEIG_REQUIRE(!(minv && plan.split), "the preconditioned solve does not take a column-split TCOO-W layout");
   if (const int rc = minv ? minres_ka_lds_limits<1>(plan) : minres_ka_lds_limits<0>(plan)) return rc;

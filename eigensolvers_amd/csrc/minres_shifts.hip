@@ -304,7 +304,8 @@ extern "C" int hipeig_minres_shifts(hipeig_ctx* c, hipeig_csr* A, double sign, i
   if (hipeig_sync_checked(c)) return 4;                        // the pinned record is rewritten by the first chunk's copy-back
 
   SweepPlan plan;
-  if (const int rc = sweep_plan_build(c, A, 8, &plan)) return rc;             // combine launch of a column-split sweep: minres.hip's grid
+  if (const int rc = sweep_plan_build(c, A, grid_wide(n, 8), &plan)) return rc;   // combine launch of a column-split sweep: minres.hip's grid
+  HIPEIG_REQUIRE(plan.nPA <= HIPEIG_WIDE_PARTIALS, "too many sweeps for the partial-sum buffer");
   if (const int rc = sweep_set_lds_limits(plan, (const void*)ms_sweep_kernel<3>, (const void*)ms_sweep_kernel<4, 0>,
                                           (const void*)ms_sweep_kernel<4, 1>)) return rc;
   const int gE = grid_wide(n, env_int("HIPEIG_MS_PER_THREAD", 8));         // KC: its reduction finishes in the last workgroup

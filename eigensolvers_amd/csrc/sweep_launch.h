@@ -1,23 +1,26 @@
-// Host side of "one operator sweep of a single vector with a row epilogue and one reduced scalar": the iteration sweeps of
-// the MINRES drivers (minres.hip, minres_shifts.hip).  The caller owns the kernel - a template over (VARIANT, FIXED) as
-// minres_ka_kernel - and its arguments; the layout, the grids, the exchange and the order of the launches live here, once.
-//   SweepPlan plan;  sweep_plan_build(c, A, rows_per_thread, &plan);  sweep_set_lds_limits(plan, k<3>, k<4,0>, k<4,1>);
+// Host side of "one operator sweep of a single vector with a row epilogue": the product and shifted product of spmv.hip
+// (no reduction) and the iteration sweeps of the MINRES drivers (minres.hip, minres_shifts.hip: one reduced scalar).  The
+// caller owns the kernel - a template over (VARIANT, FIXED) as minres_ka_kernel, or named kernels picked with `if constexpr` as
+// spmv_launcher - and its arguments; the layout, the grids,
+// the exchange and the order of the launches live here, once.
+//   SweepPlan plan;  sweep_plan_build(c, A, combine_grid, &plan);  sweep_set_lds_limits(plan, k<3>, k<4,0>, k<4,1>);
 //   per sweep:  sweep_prepare(...)  (exchange, waits, raw launches; hands back the gathered operand)
 //               sweep_launch(...)   (the epilogue launches, then the combine launch of a column-split sweep)
-// hipeig_spmv's launch_spmv (spmv.hip) launches reduction-free kernels of its own and does not come through here; the
-// sweeps of interleaved blocks have their own launcher, block_sweep_launch.h.
+// The product raises the LDS limits of its kernels where the layouts are built, not per product.  The sweeps of interleaved
+// blocks have their own launcher, block_sweep_launch.h; the pair sweep (two accumulators per row, no split, no exchange)
+// keeps its loop in spmv.hip.
 #pragma once
 #include <type_traits>
 #include "spmv_device.h"
 
 CsrView hipeig_csr_view(const hipeig_csr* A);
 TcooView hipeig_tcoo_view(const hipeig_csr* A, const BlockedLayout& L);
-int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const double* x_local, int fixed, TcooView* last, bool* has_last,
-                          const double** xg, int* ncombine);
 int hipeig_tcoow_reserve(hipeig_ctx* c, const hipeig_csr* A);
 SweepGrid hipeig_sweep_grid(const hipeig_csr* A, int variant);
 int hipeig_csr_pick_variant(hipeig_ctx* c, hipeig_csr* A);
 size_t hipeig_tcoo_lds_bytes(const hipeig_csr* A);
+void hipeig_phase_mark(hipeig_ctx* c, int k);
+const double* hipeig_gathered(hipeig_ctx* c);
 
 struct SweepPlan {
   int variant;               // 1-4 (the public variant 5 is 4 with `fixed`)
@@ -28,11 +31,13 @@ struct SweepPlan {
   int gA, nsweep;            // workgroups per sweep launch, sweep launches
   bool split;                // column-split TCOO-W: raw slabs + a combine launch that carries the epilogue
   int gC;                    // grid of that combine launch
-  int nPA;                   // partials of the reduced scalar one sweep leaves (side by side, one per workgroup)
+  int nPA;                   // workgroups whose epilogue runs in one sweep: the partials a reducing kernel leaves, side by side
 };
 
-// Picks the layout (building the blocked copy on demand) and sizes one sweep of A.
-static inline int sweep_plan_build(hipeig_ctx* c, hipeig_csr* A, int combine_rows_per_thread, SweepPlan* p) {
+// Picks the layout (building the blocked copy on demand) and sizes one sweep of A.  `combine_grid`: the grid of the combine
+// launch of a column-split sweep, the caller's because it depends on what the epilogue carries.  A caller whose kernel leaves
+// a partial per workgroup requires nPA <= HIPEIG_WIDE_PARTIALS itself.
+static inline int sweep_plan_build(hipeig_ctx* c, hipeig_csr* A, int combine_grid, SweepPlan* p) {
   p->variant = hipeig_csr_pick_variant(c, A);
   if (p->variant < 0) return 1;
   p->fixed = (p->variant == 5) ? 1 : 0;
@@ -45,9 +50,8 @@ static inline int sweep_plan_build(hipeig_ctx* c, hipeig_csr* A, int combine_row
   const SweepGrid sg = hipeig_sweep_grid(A, p->variant);
   p->gA = sg.wgs; p->nsweep = sg.launches;
   p->split = (p->variant == 4) && A->w.csplit > 1;
-  p->gC = grid_wide(A->nrows, combine_rows_per_thread);
+  p->gC = combine_grid;
   p->nPA = p->split ? p->gC : p->gA * p->nsweep;
-  HIPEIG_REQUIRE(p->nPA <= HIPEIG_WIDE_PARTIALS, "too many sweeps for the partial-sum buffer");
   return 0;
 }
 
@@ -69,18 +73,21 @@ struct SweepOperand {
   int ncombine;              // slabs the combine launch adds (0: none)
 };
 
+// spmv.hip: the exchange and every launch of a TCOO-W sweep that carries no epilogue (product kernels with the empty one)
+int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const SweepPlan& p, const double* x_local, SweepOperand* o);
+
 // Everything of one sweep that comes before its epilogue launches: the operand exchange with its waits and, for TCOO-W,
 // the raw launches of the plan (own windows under the exchange, chunk by chunk behind it).
 static inline int sweep_prepare(hipeig_ctx* c, hipeig_csr* A, const SweepPlan& p, const double* x_local, SweepOperand* o) {
   o->xg = nullptr; o->tv = p.tview; o->has_last = true; o->ncombine = 0;
-  if (p.variant == 4) return hipeig_tcoow_run_plan(c, A, x_local, p.fixed, &o->tv, &o->has_last, &o->xg, &o->ncombine) ? 4 : 0;
+  if (p.variant == 4) return hipeig_tcoow_run_plan(c, A, p, x_local, o) ? 4 : 0;
   return hipeig_allgather_x(c, A->gl, x_local, A->nrows, &o->xg) ? 4 : 0;
 }
 
 // The epilogue launches of one sweep.  `launch(variant, fixed, grid, threads, lds_bytes, tview, xg, partial_offset)` is
 // called once per kernel launch with the first two as std::integral_constant, so that the caller's generic lambda names
-// its kernel as kernel<decltype(variant)::value, decltype(fixed)::value>; workgroup b of that launch owns partial
-// partial_offset + b of the plan's nPA.
+// its kernel as kernel<decltype(variant)::value, decltype(fixed)::value> (variant 5: the combine step, tcoow_combine_sweep on
+// tview.raw_out / part_base / part_stride); workgroup b of that launch owns partial partial_offset + b of the plan's nPA.
 template <class Launch>
 static inline void sweep_launch(hipeig_ctx* c, const SweepPlan& p, const SweepOperand& o, Launch&& launch) {
   using std::integral_constant;

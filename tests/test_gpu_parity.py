@@ -11,6 +11,7 @@ import pytest
 import scipy.linalg as la
 import scipy.sparse as sp
 
+from _sweep_cases import check_kernel_forms
 from conftest import load_golden
 from eigensolvers_amd.generators import dense_test_matrix, gapped_csr_host
 from oracle import lanczos_ref
@@ -335,13 +336,7 @@ def test_minres_two_and_three_kernel_forms_agree_in_every_sweep_layout(hip, monk
         monkeypatch.delenv("HIPEIG_MINRES_FUSE_KD")
         if csplit:
             monkeypatch.delenv("HIPEIG_TCOOW_CSPLIT")
-        assert s2["iterations"] == s3["iterations"] == itn and s2["istop"] == s3["istop"] == istop, (variant, csplit)
-        scale = np.linalg.norm(xo)
-        assert np.linalg.norm(x2 - x3) <= 1e-7 * scale, (variant, csplit)      # variant 4 adds a row in varying order
-        assert np.linalg.norm(x2 - xo) <= 1e-6 * scale, (variant, csplit)
-        if variant in (1, 2, 3, 5) and not csplit:                             # fixed summation order: bit for bit (a scalar's
-            # summation tree does not depend on which kernel's prologue reduces it, common.h block_sum_partials)
-            np.testing.assert_array_equal(x2, x3)
+        check_kernel_forms((variant, csplit), variant in (1, 2, 3, 5) and not csplit, x2, s2, x3, s3, xo, itn, istop)
 
 
 def test_minres_graph_replay_is_bit_identical(hip, gapped4000, monkeypatch):

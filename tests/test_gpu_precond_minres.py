@@ -10,6 +10,7 @@ import pytest
 import scipy.sparse as sp
 
 import _precond_cases as pc
+from _sweep_cases import check_against_twin as _check_against_twin, within as _within
 from eigensolvers_amd.generators import gapped_csr_host, guess_vector
 from eigensolvers_amd.precond_minres import csr_diagonal_host, jacobi_inverse_host
 
@@ -22,28 +23,6 @@ def _opts(it=2000, tol=1e-10, pre="jacobi", **lsa):
         d["preconditioner"] = pre
     d.update(lsa)
     return {"linearSystemArgs": d}
-
-
-def _within(got, ref, bound):
-    err = np.abs(np.asarray(got) - np.asarray(ref))
-    assert (err <= bound).all(), f"max excess {np.max(err - bound):.3e}, {int((err > bound).sum())} elements"
-
-
-def _check_against_twin(label, Hh, b, sigma, rtol, W, tw, sign=1.0):
-    xo, info, itn, istop, trace = tw
-    st = W.last_solve_stats
-    x = W.array
-    r = np.linalg.norm(b - sign * (sigma * x - Hh @ x))
-    ro = np.linalg.norm(b - sign * (sigma * xo - Hh @ xo))
-    print(f"PMR {label}: iterations {st['iterations']} (twin {itn}), istop {st['istop']} ({istop}), |x - twin| / |x| = "
-          f"{np.linalg.norm(x - xo) / np.linalg.norm(xo):.2e}, rnorm {st['rnorm']:.3e} ({trace[-1]['rnorm']:.3e}), Anorm "
-          f"{st['Anorm']:.6e} ({trace[-1]['Anorm']:.6e}), true residual {r:.3e} ({ro:.3e})")
-    assert st["preconditioner"] == "jacobi"
-    assert st["iterations"] == itn and st["istop"] == istop
-    _within(x, xo, max(1e-9, 100 * rtol) * np.linalg.norm(xo))
-    assert abs(st["rnorm"] - trace[-1]["rnorm"]) <= 0.05 * trace[-1]["rnorm"]
-    assert r <= 1.05 * ro + 1e-13
-    assert abs(st["Anorm"] - trace[-1]["Anorm"]) <= 1e-3 * trace[-1]["Anorm"]
 
 
 # ---------------------------------------------------------------- N = 4000: tracks the twin

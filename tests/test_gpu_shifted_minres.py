@@ -14,27 +14,16 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from _sweep_cases import (CONTOUR, EPS, REAL_SHIFT, SHIFT_SETS, check_residuals, residual_bound, shifted_options as options,
+                          true_residual)
 from conftest import load_golden
-from eigensolvers_amd import feast as pf
 from eigensolvers_amd.generators import gapped_csr_host, gapped_params
 from eigensolvers_amd.shifted_minres import shifted_minres_host
 
 pytestmark = pytest.mark.gpu
 
-EPS = np.finfo(float).eps
-REAL_SHIFT = 0.5
 TOLS = [(1e-5, 1e-7), (1e-10, 1e-12)]
 STEP_DIFFERENCE_BOUND = 3          # max(3, 2 * largest difference observed), see the module docstring
-
-
-def contour_shifts():
-    gk, _ = pf.quadraturePointsWeights(16, "legendre", positiveHalf=True)
-    return [pf.contour_point(-0.21, 0.21, g)[1] for g in gk]
-
-
-CONTOUR = contour_shifts()
-SHIFT_SETS = {1: [CONTOUR[7]], 3: [CONTOUR[0], REAL_SHIFT, CONTOUR[5]], 8: CONTOUR[:3] + [REAL_SHIFT] + CONTOUR[4:],
-              9: CONTOUR + [REAL_SHIFT]}                      # 9: two calls of the C entry (8 + 1)
 
 
 def odd_operator():
@@ -77,29 +66,6 @@ def twin(name, Hh, b, shifts, rtol, atol, sign, maxiter=4000):
     if key not in _twin_cache:
         _twin_cache[key] = shifted_minres_host(lambda v: Hh @ v, b, shifts, rtol, atol, maxiter, sign)
     return _twin_cache[key]
-
-
-def options(rtol, atol, maxiter=4000):
-    return {"linearSystemArgs": {"linearSolver": "minres_shifted", "linearIter": maxiter, "linear_tol": rtol,
-                                 "linear_atol": atol}}
-
-
-def residual_bound(Hh, z, x, target):
-    hinf = abs(Hh).sum(axis=1).max()
-    return 1.01 * target + 100 * EPS * (abs(z) + hinf) * np.linalg.norm(x)
-
-
-def true_residual(Hh, b, z, x, sign):
-    return np.linalg.norm(b - sign * (z * x - Hh @ x))
-
-
-def check_residuals(Hh, b, shifts, xs, sign, rtol, atol):
-    target = max(atol, rtol * np.linalg.norm(b))
-    for z, x in zip(shifts, xs):
-        xa = x.array
-        assert xa.dtype == np.complex128 and np.isfinite(xa).all()
-        res = true_residual(Hh, b, z, xa, sign)
-        assert res <= residual_bound(Hh, z, xa, target), (z, res, target)
 
 
 @pytest.mark.parametrize("rtol,atol", TOLS)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from _sweep_cases import fixed_point_term, product_bound as _bound
 from conftest import REPO
 from eigensolvers_amd.distributed import LoopbackGroup, row_range
 
@@ -36,10 +37,6 @@ def _edge_matrix(N, seed):
     A.sum_duplicates()
     A.sort_indices()
     return A
-
-
-def _bound(A, x):
-    return 4e-14 * (abs(A) @ np.abs(x)) + 1e-300
 
 
 def _product(hip, H, x, variant):
@@ -102,7 +99,7 @@ def test_fixed_point_is_bitwise_equal_across_layout_builds(hip, monkeypatch):
         y = _product(hip, H, x, 5)
         assert H.last_variant() == "column-window-blocked(workgroup, fixed-point)"
         np.testing.assert_array_equal(y, _product(hip, H, x, 5))
-        assert np.all(np.abs(y - ref) <= _bound(A, x) + 40 * 2.0 ** -60 * abs(A).sum(axis=1).max() * np.max(np.abs(x)))
+        assert np.all(np.abs(y - ref) <= _bound(A, x) + fixed_point_term(A, x))
         outs.append(y)
     np.testing.assert_array_equal(outs[0], outs[1])
 
@@ -175,7 +172,7 @@ def test_loopback_ranks_with_small_windows(hip, monkeypatch, csplit):
         assert o["layout"]["column_splits"] == (csplit or 1)
         for variant in (1, 4):
             assert np.all(np.abs(o[variant] - ref[b:e]) <= bound[b:e]), (r, variant)
-        assert np.all(np.abs(o[5] - ref[b:e]) <= bound[b:e] + 40 * 2.0 ** -60 * abs(A).sum(axis=1).max() * np.max(np.abs(x)))
+        assert np.all(np.abs(o[5] - ref[b:e]) <= bound[b:e] + fixed_point_term(A, x))
 
 
 @pytest.mark.parametrize("N,nnz_row", [(1_000_000, 32), (10_000_000, 64)])

@@ -99,7 +99,8 @@ def rel(a, b):
     return 0.0 if a.shape == b.shape and np.array_equal(a, b) else float(np.max(np.abs(a - b)) / np.max(np.abs(a))) if a.shape == b.shape else math.inf
 
 
-def compare(pa, pb, br, jsonl):
+def compare(pa, pb, br, jsonl, fixed_order=lambda case: case.split("/")[0] == "1"):
+    """``fixed_order(case)``: the case adds a row's terms in a fixed order, so it must reproduce the parent bit for bit."""
     A, B, C = np.load(pa), np.load(pb), np.load(br)
     assert set(A.files) == set(B.files) == set(C.files), "the runs hold different cases"
     rows, ok = [], True
@@ -111,11 +112,11 @@ def compare(pa, pb, br, jsonl):
         parent_counts_equal = all(np.array_equal(A[k], B[k]) for k in ints)     # the parent against itself
         yard = max([rel(A[k], B[k]) for k in reals], default=0.0)
         diff = max([rel(A[k], C[k]) for k in reals], default=0.0)
-        fixed_order = case.split("/")[0] == "1"
-        good = counts_equal and (diff == 0.0 and yard == 0.0 if fixed_order else diff <= 4.0 * yard)
+        fixed = fixed_order(case)
+        good = counts_equal and (diff == 0.0 and yard == 0.0 if fixed else diff <= 4.0 * yard)
         ok = ok and good
         row = {"case": case, "counts_equal": bool(counts_equal), "parent_counts_equal": bool(parent_counts_equal), "parent_vs_parent": yard, "branch_vs_parent": diff,
-               "criterion": "bit-equal" if fixed_order else "branch <= 4 x parent", "ok": bool(good)}
+               "criterion": "bit-equal" if fixed else "branch <= 4 x parent", "ok": bool(good)}
         if ints:
             row["counts"] = A[ints[0]].tolist()
             if not (counts_equal and parent_counts_equal):
