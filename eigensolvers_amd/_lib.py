@@ -107,6 +107,7 @@ SIGNATURES = {
     "hipeig_minres_jacobi": [_P, _P, _D, _D, _P, _P, _P, _D, C.c_int, _IP, _DP],
     "hipeig_dense_solve_small": [_P, _P, _D, _D, _D, _P, _P, _P, _P, _IP],
     "hipeig_minres_block": [_P, _P, _D, _D, C.c_int, _PP, _PP, _D, C.c_int, _IP, _DP],
+    "hipeig_minres_block_jacobi": [_P, _P, _D, _D, C.c_int, _PP, _P, _PP, _D, C.c_int, _IP, _DP],
     "hipeig_minres_shifts": [_P, _P, _D, C.c_int, _DP, _DP, _P, _PP, _PP, _D, _D, C.c_int, _IP, _DP],
     "hipeig_lanczos_block_scalars": [_P, _P, _D, C.c_int, _PP, C.c_int, _DP, _DP, _D, _D, C.c_int, _DP, _DP, _IP, _DP, _IP,
                                      _DP, C.c_int, _I64, _PP],

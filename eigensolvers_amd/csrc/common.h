@@ -45,7 +45,7 @@ enum : int {
   // first row of every rank, as int64 (operator set-up).  spmv.hip spells this offset as the literal 1024: its bytes are
   // part of the signature that ties profiles/pmc_current.json to the sweep sources (bench.py, kernel_signature).
   SC_GATHER_OFFS = 1024,   SC_GATHER_OFFS_LEN = HIPEIG_MAX_RANKS + 1,
-  SC_COMM = 2048,          SC_COMM_LEN = 32,            // block MINRES's all-reduce records (minres_block.hip)
+  SC_COMM = 2048,          SC_COMM_LEN = 32,            // block MINRES's all-reduce records (minres_block.hip); one GPU: the K <b_j, z_0j> of minres_block_precond.hip
   SC_COMM_BENCH_LEN = 1024,                             // hipeig_comm_bench_allreduce takes up to this much from SC_COMM
   SC_ARN_RESULT = 2560,    SC_ARN_RESULT_LEN = 1040,    // the Arnoldi step's result record / the projection's coefficients
   SC_MINRES_TOT = 3072,    SC_MINRES_TOT_LEN = 8,       // MINRES and shifted MINRES: totals of the iteration's reductions
@@ -164,6 +164,10 @@ struct hipeig_ctx {
   int64_t mrb_ws_n;
   MinresState* d_mrb_state;  // ring of 3 x 8 records
   MinresState* h_mrb_state;  // pinned, 8 records
+  // Jacobi-preconditioned block MINRES (minres_block_precond.hip): a ring of two interleaved z = M^-1 r2 blocks in a buffer
+  // of its own, so that the seven blocks above are the plain block solve's whatever ran before; mrbz_ws_n is their stride
+  double* mrbz_ws;
+  int64_t mrbz_ws_n;
   int overlap;               // 1: all-gather on the comm stream while the local-column windows are swept
   double* ytmp;              // raw partial sums handed from the local-window launch to the remote one
   int64_t ytmp_n;

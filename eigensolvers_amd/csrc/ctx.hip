@@ -91,6 +91,7 @@ extern "C" int hipeig_ctx_destroy(hipeig_ctx* c) {
   if (c->mrb_ws) hipFree(c->mrb_ws);
   if (c->d_mrb_state) hipFree(c->d_mrb_state);
   if (c->h_mrb_state) hipHostFree(c->h_mrb_state);
+  if (c->mrbz_ws) hipFree(c->mrbz_ws);
   if (c->ms_ws) hipFree(c->ms_ws);
   if (c->h_ms_state) hipHostFree(c->h_ms_state);
   if (c->lf_ws) hipFree(c->lf_ws);

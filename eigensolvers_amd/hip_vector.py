@@ -31,8 +31,16 @@ PRECONDITIONER_FLOOR_DEFAULT = 1e-8      # relative; only a guard against h_ii =
 
 def _preconditioner(o, sigma=None, x0=None, ctx=None):
     """``o["preconditioner"]`` of a ``linearSystemArgs`` dict, validated: ``None`` or ``"jacobi"``.  The key belongs to
-    the real-shift single-vector MINRES solve on one GPU; every other combination raises instead of doing something else."""
+    the real-shift single-vector MINRES solve on one GPU; every other combination raises instead of doing something else.
+    ``o["preconditionerLockStep"]`` (``solveBlock``'s lock-step block form of that solve) is validated with it: a ``bool``,
+    and ``True`` only together with ``"preconditioner": "jacobi"``."""
     pre = o.get("preconditioner")
+    lock_step = o.get("preconditionerLockStep", False)
+    if not isinstance(lock_step, (bool, np.bool_)):
+        raise ValueError(f'linearSystemArgs["preconditionerLockStep"] must be a bool, got {lock_step!r}')
+    if lock_step and pre is None:
+        raise ValueError('linearSystemArgs["preconditionerLockStep"] asks for the lock-step block form of the '
+                         'preconditioned MINRES: it needs "preconditioner": "jacobi"')
     if pre is None:
         return None
     if pre != "jacobi":
@@ -858,9 +866,29 @@ class HipVector(AbstractVector):
         (width, rounds, block products by live operands, products and outer iterations per solve) when the pool ran.
 
         With ``linearSystemArgs["preconditioner"]`` set the solves are the one-by-one ``solve`` calls whatever the block
-        size: the lock-step block kernel has no preconditioned form yet."""
+        size, unless ``linearSystemArgs["preconditionerLockStep"]`` is ``True`` (default ``False``; a ``bool``, and only with
+        ``"preconditioner": "jacobi"`` - anything else raises ``ValueError``).  Then one real shift, no ``x0``, at least
+        ``BLOCK_SOLVE_MIN`` right-hand sides, a ``HipCsrOperator`` and a context without collectives run the lock-step
+        block form of the preconditioned solve (``hipeig_minres_block_jacobi``) in chunks of 8, the 4-wide
+        interleave for 4 or fewer: every column runs the recurrence and stopping tests of the preconditioned single solve,
+        ``M`` is the single solve's (``H.jacobi_inverse``), and ``last_solve_stats`` gains ``"preconditioner": "jacobi"``
+        and ``"lockStep": True``.  A block product adds a row in another order than the single sweep, so the results agree
+        with the one-by-one solves to the solve tolerance, not bit for bit; every other case takes the one-by-one calls
+        with their refusals."""
         bs = list(bs)
         if bs and _preconditioner(bs[0].options["linearSystemArgs"]) is not None:
+            o = bs[0].options["linearSystemArgs"]
+            if (o.get("preconditionerLockStep", False) and np.ndim(sigma) == 0
+                    and not (isinstance(sigma, complex) or np.iscomplexobj(sigma)) and x0 is None
+                    and len(bs) >= HipVector.BLOCK_SOLVE_MIN and isinstance(H, HipCsrOperator)
+                    and all(isinstance(b, HipVector) for b in bs)
+                    and not bs[0].ctx.collectives and not bs[0].ctx.direct_only):
+                sols = HipVector._solve_block_minres(H, bs, float(sigma), o, reverseGF, jacobi=True)
+                if onSolution is not None:
+                    for i, xs in enumerate(sols):
+                        onSolution(i, xs)
+                    return [None] * len(sols)
+                return sols
             # one by one whatever the block size: every refusal and result is that of solve()
             shifts = list(sigma) if np.ndim(sigma) > 0 else [sigma] * len(bs)
             if len(shifts) != len(bs):
@@ -900,8 +928,16 @@ class HipVector(AbstractVector):
                 or x0 is not None or len(bs) < HipVector.BLOCK_SOLVE_MIN or not isinstance(H, HipCsrOperator)
                 or bs[0].ctx.direct_only):
             return [HipVector.solve(H, b, sigma, x0, opType, reverseGF) for b in bs]
+        return HipVector._solve_block_minres(H, bs, float(sigma), o, reverseGF)
+
+    @staticmethod
+    def _solve_block_minres(H, bs, sigma, o, reverseGF, jacobi=False):
+        """The lock-step MINRES solves of ``solveBlock`` in chunks of 8 right-hand sides: ``hipeig_minres_block``, or with
+        ``jacobi`` its preconditioned form ``hipeig_minres_block_jacobi`` with the single solve's ``M^-1``."""
         H.honour_reduction_option(bs[0].options)
         ctx, n = bs[0].ctx, bs[0]._buf.n
+        if jacobi:
+            minv = H.jacobi_inverse(sigma, float(o.get("preconditionerFloor", PRECONDITIONER_FLOOR_DEFAULT)))
         results = []
         for i0 in range(0, len(bs), 8):
             chunk = bs[i0:i0 + 8]
@@ -911,8 +947,12 @@ class HipVector(AbstractVector):
             xt, keep2 = _ptr_table(outs)
             info = (C.c_int * k)()
             stats = (C.c_double * (8 * k))()
-            _lib.call("hipeig_minres_block", ctx.handle, H.handle, float(sigma), -1.0 if reverseGF else 1.0, k,
-                      bt, xt, float(o["linear_tol"]), int(o["linearIter"]), info, stats)
+            if jacobi:
+                _lib.call("hipeig_minres_block_jacobi", ctx.handle, H.handle, sigma, -1.0 if reverseGF else 1.0, k,
+                          bt, minv.ptr, xt, float(o["linear_tol"]), int(o["linearIter"]), info, stats)
+            else:
+                _lib.call("hipeig_minres_block", ctx.handle, H.handle, sigma, -1.0 if reverseGF else 1.0, k,
+                          bt, xt, float(o["linear_tol"]), int(o["linearIter"]), info, stats)
             ncoll = None
             if ctx.nranks > 1 or os.environ.get("HIPEIG_FORCE_COLLECTIVES", "0") not in ("", "0"):
                 cs = (C.c_int64 * 4)()
@@ -926,6 +966,9 @@ class HipVector(AbstractVector):
                     "ynorm": st[4], "test1": st[5], "test2": st[6], "Acond": st[7]}
                 if ncoll is not None:
                     res.last_solve_stats["collectives"] = ncoll
+                if jacobi:
+                    res.last_solve_stats["preconditioner"] = "jacobi"
+                    res.last_solve_stats["lockStep"] = True
                 results.append(res)
             if any(info[j] != 0 for j in range(k)):
                 raise UserWarning("Warning:: Iterative solver is not converged ")

@@ -6,6 +6,9 @@ evaluation the device uses: ``z = minv * r2`` is a vector of its own, the Lanczo
 ``minres`` without ``M`` (numpyVector.py:163), so this path has no counterpart there; SciPy itself is the referee
 (``tests/test_precond_minres_cpu.py``).
 
+``minres_jacobi_block_host`` is the lock-step block form (``csrc/minres_block_precond.hip``): the same recurrence for the
+columns of an ``[n, k]`` array with one block product per iteration, every column masked once it has stopped.
+
 ``jacobi_inverse_host`` is the NumPy statement of ``hipeig_jacobi_inverse`` and ``csr_diagonal_host`` that of
 ``hipeig_csr_diagonal``.
 """
@@ -158,3 +161,110 @@ def minres_jacobi_host(matvec, b, minv, rtol=1e-5, maxiter=None, trace=None):
 
     info = maxiter if istop == 6 else 0
     return x, info, itn, istop
+
+
+def minres_jacobi_block_host(matvec_block, B, minv, rtol=1e-5, maxiter=None):
+    """The lock-step block form of ``minres_jacobi_host`` (``csrc/minres_block_precond.hip``): the columns of ``B``
+    (``[n, k]``) advance together, one ``matvec_block`` (``[n, k] -> [n, k]``) per iteration.  Every column keeps its own
+    scalars and stopping tests; a column that has stopped (or whose ``<b, M^-1 b>`` is 0) is masked - its Lanczos vector is
+    sent into the product as zeros and its iterate is no longer touched.  Returns one ``(x, info, itn, istop)`` per
+    column: with a ``matvec_block`` that applies ``matvec`` column by column, the bits of ``minres_jacobi_host``."""
+    B = np.asarray(B, dtype=np.float64)
+    minv = np.asarray(minv, dtype=np.float64)
+    n, k = B.shape
+    if maxiter is None:
+        maxiter = 5 * n
+    eps = np.finfo(np.float64).eps
+
+    def dots(P, Q, cols):                               # per column, on contiguous copies: the bits of the single twin's np.dot
+        return {j: float(np.dot(np.ascontiguousarray(P[:, j]), np.ascontiguousarray(Q[:, j]))) for j in cols}
+
+    X = np.zeros((n, k))
+    R2 = B.copy()
+    Z = minv[:, None] * R2                              # start kernel
+    st = []
+    for j, bz in dots(R2, Z, range(k)).items():
+        if bz < 0:
+            raise ValueError("indefinite preconditioner")
+        beta1 = math.sqrt(bz)
+        st.append(dict(live=bz != 0.0, beta1=beta1, oldb=0.0, beta=beta1, dbar=0.0, epsln=0.0, phibar=beta1, tnorm2=0.0,
+                       gmax=0.0, gmin=np.finfo(np.float64).max, cs=-1.0, sn=0.0, istop=0, itn=0))
+    W = np.zeros((n, k))
+    W2 = np.zeros((n, k))
+    R1 = R2
+    itn = 0
+
+    def coef(f):                                        # one coefficient per column, 0 for a masked one
+        return np.array([f(S) if S["live"] else 0.0 for S in st])
+
+    while itn < maxiter and any(S["live"] for S in st):
+        itn += 1
+        live = [j for j in range(k) if st[j]["live"]]
+        V = coef(lambda S: 1.0 / S["beta"]) * Z         # KA': the sweep gathers Z
+        Y = matvec_block(V)
+        if itn >= 2:
+            Y = Y - coef(lambda S: S["beta"] / S["oldb"]) * R1
+        for j, alfa in dots(V, Y, live).items():
+            st[j]["alfa"] = alfa
+        Y = Y - coef(lambda S: S["alfa"] / S["beta"]) * R2     # KC'
+        R1 = R2
+        R2 = Y
+        Z = minv[:, None] * R2
+        yz = dots(R2, Z, live)
+        oldeps, delta, denom, phi = np.zeros(k), np.zeros(k), np.zeros(k), np.zeros(k)
+        for j in live:
+            S = st[j]
+            S["itn"] = itn
+            S["oldb"] = S["beta"]
+            if yz[j] < 0:
+                raise ValueError("non-symmetric matrix")
+            S["beta"] = math.sqrt(yz[j])
+            alfa, oldb, beta = S["alfa"], S["oldb"], S["beta"]
+            S["tnorm2"] += alfa * alfa + oldb * oldb + beta * beta
+            if itn == 1 and beta / S["beta1"] <= 10 * eps:
+                S["istop"] = -1
+            oldeps[j] = S["epsln"]
+            delta[j] = S["cs"] * S["dbar"] + S["sn"] * alfa
+            gbar = S["sn"] * S["dbar"] - S["cs"] * alfa
+            S["epsln"] = S["sn"] * beta
+            S["dbar"] = -S["cs"] * beta
+            S["root"] = math.sqrt(gbar * gbar + S["dbar"] * S["dbar"])
+            gamma = max(math.sqrt(gbar * gbar + beta * beta), eps)
+            S["cs"] = gbar / gamma
+            S["sn"] = beta / gamma
+            phi[j] = S["cs"] * S["phibar"]
+            S["phibar"] = S["sn"] * S["phibar"]
+            denom[j] = 1.0 / gamma
+            S["gmax"] = max(S["gmax"], gamma)
+            S["gmin"] = min(S["gmin"], gamma)
+        W1 = W2                                         # KD
+        W2 = W
+        W = (V - oldeps * W1 - delta * W2) * denom
+        X[:, live] = X[:, live] + phi[live] * W[:, live]
+        for j, xx in dots(X, X, live).items():
+            S = st[j]
+            Anorm = math.sqrt(S["tnorm2"])
+            ynorm = math.sqrt(xx)
+            epsx = Anorm * ynorm * eps
+            test1 = math.inf if (ynorm == 0 or Anorm == 0) else S["phibar"] / (Anorm * ynorm)
+            test2 = math.inf if Anorm == 0 else S["root"] / Anorm
+            Acond = S["gmax"] / S["gmin"]
+            if S["istop"] == 0:
+                if 1 + test2 <= 1:
+                    S["istop"] = 2
+                if 1 + test1 <= 1:
+                    S["istop"] = 1
+                if itn >= maxiter:
+                    S["istop"] = 6
+                if Acond >= 0.1 / eps:
+                    S["istop"] = 4
+                if epsx >= S["beta1"]:
+                    S["istop"] = 3
+                if test2 <= rtol:
+                    S["istop"] = 2
+                if test1 <= rtol:
+                    S["istop"] = 1
+            if S["istop"] != 0:
+                S["live"] = False
+
+    return [(X[:, j].copy(), maxiter if S["istop"] == 6 else 0, S["itn"], S["istop"]) for j, S in enumerate(st)]

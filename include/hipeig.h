@@ -336,6 +336,16 @@ int hipeig_minres_block(hipeig_ctx* ctx, hipeig_csr* A, double sigma, double sig
                         const double* const* b, double* const* x, double rtol, int maxiter,
                         int* info, double* out_stats);
 
+/* hipeig_minres_block with SciPy's M = diag(1 / minv) (opt-in: linearSystemArgs["preconditionerLockStep"]): column j runs
+ * the recurrences and stopping tests of hipeig_minres_jacobi on b[j] - z = minv (.) r2, beta^2 = <r2, z>, rtol tested in
+ * the preconditioned quantities - on interleaved blocks, one block product per iteration; a column with <b, minv (.) b>
+ * == 0 returns x = 0 after 0 iterations, a negative or not-a-number one fails.  minv: hipeig_jacobi_inverse's vector
+ * (n doubles), shared by the columns.  info and out_stats as in hipeig_minres_block.  One GPU, whole vectors, a square
+ * operator: a context with collectives is refused.                                                                */
+int hipeig_minres_block_jacobi(hipeig_ctx* ctx, hipeig_csr* A, double sigma, double sign, int k,
+                               const double* const* b, const double* minv, double* const* x,
+                               double rtol, int maxiter, int* info, double* out_stats);
+
 /* Shifted MINRES: sign*(z_j I - H) x_j = b for nshift (1..8) shifts z_j = zr[j] + i zi[j] - real (zi = 0) or complex -
  * of one real symmetric operator and one real right-hand side, all from ONE Lanczos run on H: one operator product per
  * step whatever nshift is.  Each shift keeps a complex rotation recurrence and a three-term direction update, its

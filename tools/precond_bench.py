@@ -15,7 +15,13 @@ Times are host clocks around work that ends in a device synchronise.  The genera
 preconditioner (diagonal +-(1..10) plus a mid-spectrum cluster, off-diagonal row norm ~0.05): the iteration counts say
 nothing about operators without diagonal dominance.
 
-usage: python tools/precond_bench.py [--sizes 1000000,10000000] [--reps 3] [--no-lanczos] [--out FILE]
+With ``--block K`` it measures the block solves instead (``"what": "block"`` and ``"block_chunk"``): ``solveBlock`` on
+the same K seeded right-hand sides with ``linearSystemArgs["preconditionerLockStep"]`` off (the one-by-one preconditioned
+solves) and on (the lock-step block form), the two modes alternating inside every repetition after one warm-up each -
+ms per block of every repetition, medians and the per-column iteration counts - and the lock-step solve with
+HIPEIG_PMRB_CHUNK = 8 / 16 / 32.  The records go to ``profiles/r19_jacobi_block.jsonl`` unless ``--out`` names another file.
+
+usage: python tools/precond_bench.py [--sizes 1000000,10000000] [--reps 3] [--no-lanczos] [--block K] [--out FILE]
 """
 import argparse
 import json
@@ -104,6 +110,57 @@ def solve_records(N, nnz_row, seed, reps, emit):
     emit({"what": "floor", "N": N, "nnz_row": nnz_row, "iterations_by_preconditionerFloor": floors})
 
 
+def timed_block(H, cols, opts):
+    ctx = ea.HipContext.default()
+    B = [ea.HipVector(c, opts) for c in cols]
+    ctx.synchronize()
+    t = time.perf_counter()
+    X = ea.HipVector.solveBlock(H, B, SIGMA)
+    ctx.synchronize()
+    ms = (time.perf_counter() - t) * 1e3
+    return [x.last_solve_stats["iterations"] for x in X], bool(X[0].last_solve_stats.get("lockStep", False)), ms, X
+
+
+def block_records(N, nnz_row, seed, K, reps, emit):
+    H = ea.HipCsrOperator.generate(N, nnz_row, seed=seed)
+    cols = []
+    for j in range(K):
+        b = guess_vector(N, j + 1)
+        cols.append(b / np.linalg.norm(b))
+    modes = {"one_by_one": options(True), "lock_step": options(True)}
+    modes["lock_step"]["linearSystemArgs"]["preconditionerLockStep"] = True
+    last = {}
+    for m, o in modes.items():                                 # warm-up: code objects, layouts, workspaces, minv
+        last[m] = timed_block(H, cols, o)[3]
+    diff = [float(np.linalg.norm(a.array - b.array) / np.linalg.norm(b.array)) for a, b in zip(last["lock_step"], last["one_by_one"])]
+    del last
+    runs = {m: [] for m in modes}
+    for _ in range(reps):
+        for m, o in modes.items():                             # alternating
+            runs[m].append(timed_block(H, cols, o)[:3])
+    rec = {"what": "block", "N": N, "nnz_row": nnz_row, "seed": seed, "sigma": SIGMA, "rtol": RTOL, "reps": reps, "K": K,
+           "block_kernel": H.block_info()["variant"], "x_difference_rel_max": max(diff)}
+    for m, r in runs.items():
+        assert all(lock == (m == "lock_step") for _, lock, _ in r), "the mode did not take its path"
+        ms = [t for _, _, t in r]
+        rec[m] = {"iterations": r[0][0], "iterations_all_equal": all(i == r[0][0] for i, _, _ in r),
+                  "ms_per_block": [round(t, 4) for t in ms], "ms_per_block_median": round(median(ms), 4),
+                  "ms_per_block_spread": round(max(ms) - min(ms), 4)}
+    rec["ratio_one_by_one_over_lock_step"] = round(rec["one_by_one"]["ms_per_block_median"] / rec["lock_step"]["ms_per_block_median"], 3)
+    emit(rec)
+
+    chunks = ("8", "16", "32")
+    per = {c: [] for c in chunks}
+    for _ in range(reps):
+        for c in chunks:
+            os.environ["HIPEIG_PMRB_CHUNK"] = c
+            per[c].append(timed_block(H, cols, modes["lock_step"])[2])
+    del os.environ["HIPEIG_PMRB_CHUNK"]
+    emit({"what": "block_chunk", "N": N, "nnz_row": nnz_row, "reps": reps, "K": K,
+          "ms_per_block_median": {c: round(median(v), 4) for c, v in per.items()},
+          "ms_per_block": {c: [round(x, 4) for x in v] for c, v in per.items()}})
+
+
 def lanczos_records(emit):
     N = 1_000_000
     H = ea.HipCsrOperator.generate(N, 32, seed=7)
@@ -145,8 +202,11 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-lanczos", action="store_true")
+    ap.add_argument("--block", type=int, default=0, help="measure solveBlock on this many right-hand sides instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.block and not a.out:
+        a.out = os.path.join(REPO, "profiles", "r19_jacobi_block.jsonl")
     out = open(a.out, "a") if a.out else None
 
     def emit(rec):
@@ -159,8 +219,11 @@ def main():
     info = ea.HipContext.default().device_info()
     emit({"what": "device", "info": info if isinstance(info, (dict, list, str)) else str(info)})
     for N in [int(s) for s in a.sizes.split(",") if s]:
-        solve_records(N, a.nnz_row, a.seed, a.reps, emit)
-    if not a.no_lanczos:
+        if a.block:
+            block_records(N, a.nnz_row, a.seed, a.block, a.reps, emit)
+        else:
+            solve_records(N, a.nnz_row, a.seed, a.reps, emit)
+    if not a.no_lanczos and not a.block:
         lanczos_records(emit)
 
 
