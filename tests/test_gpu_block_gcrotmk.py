@@ -20,6 +20,7 @@ import scipy.linalg as la
 import scipy.sparse as sp
 
 import _hiprec as hp
+from _product_cases import ragged_csr as _ragged_csr
 from conftest import load_golden
 from eigensolvers_amd import _lib
 
@@ -49,18 +50,6 @@ def _gcrot_opts(it=3000, tol=1e-8, atol=1e-12, **extra):
 
 
 # ---------------------------------------------------------------- the shifted block product
-def _ragged_csr(n, seed):
-    """Odd n; empty rows, a few long rows (300 entries), the rest 0..40 entries; columns unsorted inside a row."""
-    rng = np.random.default_rng(seed)
-    lens = rng.integers(0, 41, n)
-    lens[rng.choice(n, n // 10, replace=False)] = 0
-    lens[rng.choice(n, 7, replace=False)] = 300
-    rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    col = np.concatenate([rng.choice(n, L, replace=False) for L in lens]).astype(np.int32)      # random order = unsorted
-    val = rng.standard_normal(rowptr[-1]) * np.exp(rng.uniform(-3, 3, rowptr[-1]))
-    return rowptr, col, val
-
-
 def _check_shift_block(hip, ctx, H, csr, X, ks, sigma, variants, expect_auto):
     rowptr, col, val = csr
     n = len(rowptr) - 1

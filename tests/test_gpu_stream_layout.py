@@ -11,8 +11,8 @@ import sys
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
+from _product_cases import edge_matrix as _edge_matrix
 from _sweep_cases import fixed_point_term, product_bound as _bound
 from conftest import REPO
 from eigensolvers_amd.distributed import LoopbackGroup, row_range
@@ -21,22 +21,6 @@ pytestmark = pytest.mark.gpu
 
 SMALL_UNITS = {"HIPEIG_TCOOW_RW": "64", "HIPEIG_TCOOW_WBITS": "10", "HIPEIG_TCOOW_PAIR_RW": "64",
                "HIPEIG_TCOOW_PAIR_WBITS": "10"}
-
-
-def _edge_matrix(N, seed):
-    """Sparse rows of 0..40 non-zeros: row blocks of 64 rows give (block, window) tiles of a few to ~100 slots, i.e.
-    shorter than 64 and than 256; rows 128..255 (two whole row blocks) and every 7th row are empty."""
-    rng = np.random.default_rng(seed)
-    lens = rng.integers(0, 41, N)
-    lens[128:256] = 0
-    lens[::7] = 0
-    rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    col = rng.integers(0, N, int(rowptr[-1])).astype(np.int32)
-    val = rng.standard_normal(int(rowptr[-1]))
-    A = sp.csr_matrix((val, col, rowptr), shape=(N, N))
-    A.sum_duplicates()
-    A.sort_indices()
-    return A
 
 
 def _product(hip, H, x, variant):
