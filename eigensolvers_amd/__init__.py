@@ -17,6 +17,7 @@ from .feast import feastDiagonalization
 from .lanczos import inexactLanczosDiagonalization, KrylovSpace, true_residual_norms
 from .lanczos_filter import lanczos_filter, lanczos_filter_host, lanczos_run
 from .precond_minres import csr_diagonal_host, jacobi_inverse_host, minres_jacobi_block_host, minres_jacobi_host
+from .precond_gcrotmk import jacobi_inverse_z_host
 from .shifted_minres import shifted_minres_host, solve_shifts
 from .subspace import (basisTransformation, find_nearest, get_pick_function_close_to_sigma,
                        get_pick_function_maxOvlp)
@@ -27,5 +28,6 @@ __all__ = ["AbstractVector", "LINDEP_DEFAULT_VALUE", "HipContext", "HipCsrOperat
            "basisTransformation", "find_nearest", "get_pick_function_close_to_sigma",
            "get_pick_function_maxOvlp", "shifted_minres_host", "solve_shifts",
            "lanczos_filter", "lanczos_filter_host", "lanczos_run",
-           "csr_diagonal_host", "jacobi_inverse_host", "minres_jacobi_host", "minres_jacobi_block_host"]
+           "csr_diagonal_host", "jacobi_inverse_host", "minres_jacobi_host", "minres_jacobi_block_host",
+           "jacobi_inverse_z_host"]
 __version__ = "0.1.0"

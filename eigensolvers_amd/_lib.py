@@ -100,6 +100,11 @@ SIGNATURES = {
     "hipeig_spmm_shift": [_P, _P, C.c_int, _D, _D, _PP, _PP],
     "hipeig_spmm_shift_pairs": [_P, _P, C.c_int, _D, _D, _D, _PP, _PP, _PP, _PP],
     "hipeig_spmm_shift_pairs_z": [_P, _P, C.c_int, _DP, _DP, _D, _PP, _PP, _PP, _PP],
+    "hipeig_jacobi_inverse_z": [_P, _I64, _P, _D, _D, _D, _P, _P],
+    "hipeig_diag_mul": [_P, _I64, _P, _P, _P],
+    "hipeig_pair_diag_mul": [_P, _I64, _P, _P, _P, _P, _P, _P],
+    "hipeig_spmm_shift_m": [_P, _P, C.c_int, _D, _D, _P, _PP, _PP],
+    "hipeig_spmm_shift_pairs_zm": [_P, _P, C.c_int, _DP, _DP, _D, _PP, _PP, _PP, _PP, _PP, _PP],
     "hipeig_minres": [_P, _P, _D, _D, _P, _P, _D, C.c_int, _IP, _DP],
     "hipeig_minres_x0": [_P, _P, _D, _D, _P, _P, _P, _D, C.c_int, _IP, _DP],
     "hipeig_csr_diagonal": [_P, _P, _P],

@@ -115,3 +115,19 @@ struct MinresKd {
     xv = fma(phi, wn, xv);
   }
 };
+
+// max and min over the workgroup (exact, order-free); valid in thread 0.  lds: 8 doubles.  Shared by the range passes of
+// the two Jacobi inverses (minres_precond.hip, gcrot_precond.hip).
+__device__ __forceinline__ void block_reduce_maxmin(double& mx, double& mn, double* lds) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    mx = fmax(mx, __shfl_xor(mx, off, 64));
+    mn = fmin(mn, __shfl_xor(mn, off, 64));
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) { lds[wid] = mx; lds[4 + wid] = mn; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { mx = fmax(mx, lds[w]); mn = fmin(mn, lds[4 + w]); }
+  __syncthreads();
+}

@@ -32,21 +32,6 @@ extern "C" int hipeig_csr_diagonal(hipeig_ctx* c, hipeig_csr* A, double* d) {
   return 0;
 }
 
-// max and min over the workgroup (exact, order-free); valid in thread 0.  lds: 8 doubles.
-__device__ __forceinline__ void block_reduce_maxmin(double& mx, double& mn, double* lds) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    mx = fmax(mx, __shfl_xor(mx, off, 64));
-    mn = fmin(mn, __shfl_xor(mn, off, 64));
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { lds[wid] = mx; lds[4 + wid] = mn; }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { mx = fmax(mx, lds[w]); mn = fmin(mn, lds[4 + w]); }
-  __syncthreads();
-}
-
 // t_i = |sigma - d_i|: max_i and min_i, finished in the last workgroup (common.h).  A NaN counts as +inf in the maximum,
 // which is how the host sees it (fmax would drop it).  part: 2 * gridDim.x doubles, out[0] = max, out[1] = min.
 __global__ void __launch_bounds__(HIPEIG_BLOCK)

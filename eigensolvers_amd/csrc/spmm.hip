@@ -3,6 +3,7 @@
 // (minres_block.hip) fuses its vector updates into the same sweeps.
 #include <vector>
 #include "block_sweep_launch.h"
+#include "gcrot_precond_device.h"
 
 struct PtrTable8 { const double* p[BCOO_KPACK]; };
 struct OutTable8 { double* p[BCOO_KPACK]; };
@@ -41,6 +42,49 @@ block_pack_kernel(int64_t n, int k, PtrTable8 cols, double* __restrict__ blk) {
   }
 }
 
+// The packs of the diagonally right-preconditioned GCROT products (hipeig_spmm_shift_m, hipeig_spmm_shift_pairs_zm): the
+// block receives minv (.) x instead of x, scaled with DiagMul's element as the operands stream through, so the scaling costs
+// the reads of minv and no pass of its own.  Same thread-to-element map as block_pack_kernel.
+// Real operands, one real minv for all of them.
+template <int K>
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+block_pack_scaled_kernel(int64_t n, int k, PtrTable8 cols, const double* __restrict__ minv, double* __restrict__ blk) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int j0 = (int)((((int64_t)blockIdx.x * blockDim.x + threadIdx.x) % (K / 2)) * 2);
+  const double* c0 = j0 < k ? pick8(cols, j0) : nullptr;
+  const double* c1 = j0 + 1 < k ? pick8(cols, j0 + 1) : nullptr;
+  double2* out = reinterpret_cast<double2*>(blk);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * (K / 2); t += stride) {
+    const int64_t row = t / (K / 2);
+    const double m = minv[row];
+    double2 v;
+    v.x = c0 ? DiagMul::real(m, c0[row]) : 0.0;
+    v.y = c1 ? DiagMul::real(m, c1[row]) : 0.0;
+    out[t] = v;
+  }
+}
+
+// Complex operands as (re, im) columns 2p, 2p + 1 - a thread's 16-byte pair is one complex element - each with a minv of
+// its own: M.p[2p] its real half, M.p[2p + 1] its imaginary half or null for a real minv.
+template <int K>
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+block_pack_pairs_scaled_kernel(int64_t n, int k, PtrTable8 cols, PtrTable8 M, double* __restrict__ blk) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int j0 = (int)((((int64_t)blockIdx.x * blockDim.x + threadIdx.x) % (K / 2)) * 2);
+  const bool live = j0 + 1 < k;                                      // k is even: a complex operand is there or is not
+  const double* c0 = live ? pick8(cols, j0) : nullptr;
+  const double* c1 = live ? pick8(cols, j0 + 1) : nullptr;
+  const double* m0 = live ? pick8(M, j0) : nullptr;
+  const double* m1 = live ? pick8(M, j0 + 1) : nullptr;
+  double2* out = reinterpret_cast<double2*>(blk);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * (K / 2); t += stride) {
+    const int64_t row = t / (K / 2);
+    double2 v{0.0, 0.0};
+    if (live) DiagMul::pair(m0[row], m1 ? m1[row] : 0.0, m1 != nullptr, c0[row], c1[row], v.x, v.y);
+    out[t] = v;
+  }
+}
+
 template <int K>
 __global__ void __launch_bounds__(HIPEIG_BLOCK)
 block_unpack_kernel(int64_t n, int k, const double* __restrict__ blk, OutTable8 cols) {
@@ -66,6 +110,33 @@ int hipeig_block_pack(hipeig_ctx* c, int K, int64_t n, int k, const double* cons
   if (K == 4) hipLaunchKernelGGL(block_pack_kernel<4>, dim3(g), dim3(HIPEIG_BLOCK), 0, c->stream, n, k, t, blk);
   else if (K == 8) hipLaunchKernelGGL(block_pack_kernel<8>, dim3(g), dim3(HIPEIG_BLOCK), 0, c->stream, n, k, t, blk);
   else hipLaunchKernelGGL(block_pack_kernel<16>, dim3(g), dim3(HIPEIG_BLOCK), 0, c->stream, n, k, t, blk);
+  HIPEIG_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Mre == nullptr: real operands scaled by the one vector `minv`; else k = 2 * (complex operands), columns (re, im), and
+// Mre[p], Mim[p] (may be null) the minv of complex operand p.
+static int block_pack_scaled(hipeig_ctx* c, int K, int64_t n, int k, const double* const* cols, const double* minv,
+                             const double* const* Mre, const double* const* Mim, double* blk) {
+  HIPEIG_REQUIRE((K == 4 || K == 8 || K == 16) && k >= 1 && k <= K, "a block holds 1..K operands, K = 4, 8 or 16");
+  if (n == 0) return 0;
+  PtrTable8 t, m;
+  for (int j = 0; j < BCOO_KPACK; ++j) {
+    t.p[j] = j < k ? cols[j] : nullptr;
+    m.p[j] = (Mre && j < k) ? ((j & 1) ? Mim[j / 2] : Mre[j / 2]) : nullptr;
+  }
+  const int g = grid_stream(n * (K / 2) * 2);
+  const dim3 grid(g), block(HIPEIG_BLOCK);
+  if (Mre) {
+    HIPEIG_REQUIRE(k % 2 == 0, "complex operands come as (re, im) columns");
+    if (K == 4) hipLaunchKernelGGL(block_pack_pairs_scaled_kernel<4>, grid, block, 0, c->stream, n, k, t, m, blk);
+    else if (K == 8) hipLaunchKernelGGL(block_pack_pairs_scaled_kernel<8>, grid, block, 0, c->stream, n, k, t, m, blk);
+    else hipLaunchKernelGGL(block_pack_pairs_scaled_kernel<16>, grid, block, 0, c->stream, n, k, t, m, blk);
+  } else {
+    if (K == 4) hipLaunchKernelGGL(block_pack_scaled_kernel<4>, grid, block, 0, c->stream, n, k, t, minv, blk);
+    else if (K == 8) hipLaunchKernelGGL(block_pack_scaled_kernel<8>, grid, block, 0, c->stream, n, k, t, minv, blk);
+    else hipLaunchKernelGGL(block_pack_scaled_kernel<16>, grid, block, 0, c->stream, n, k, t, minv, blk);
+  }
   HIPEIG_CHECK(hipGetLastError());
   return 0;
 }
@@ -362,11 +433,21 @@ static ShiftPairsZBlockEpilogue<K> shift_pairs_z_epilogue(const double* zr, cons
 // once per four operands instead of once each; the shift is applied in the block product's epilogue.  A row-partitioned
 // or direct-only context and npairs = 1 take hipeig_spmv_shift_pair per operand.
 // zr, zi: one shift for all operands (zstride = 0) or npairs of them (zstride = 1; hipeig_spmm_shift_pairs_z below).
+// Mre, Mim (hipeig_spmm_shift_pairs_zm only): operand p is scaled by its minv (Mre[p], Mim[p] or null) on its way into the
+// block; without them the pack, and everything else, is what it was.
 static int spmm_shift_pairs_impl(hipeig_ctx* c, hipeig_csr* A, int npairs, const double* zr, const double* zi, int zstride, double sign,
-                                 const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim) {
+                                 const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim,
+                                 const double* const* Mre = nullptr, const double* const* Mim = nullptr) {
   HIPEIG_REQUIRE(npairs >= 1 && zr && zi && Xre && Xim && Yre && Yim, "bad arguments");
   HIPEIG_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
   if (A->nrows == 0) return 0;
+  if (Mre && npairs == 1) {                           // scale into the workspace, then the single pair product
+    const int64_t n = A->ncols;
+    const size_t half = ((size_t)n + 1) & ~(size_t)1;  // keeps the second half 16-byte aligned
+    if (ensure_blk_ws(c, 2 * half)) return 1;
+    if (hipeig_pair_diag_mul(c, n, Mre[0], Mim[0], Xre[0], Xim[0], c->blk_ws, c->blk_ws + half)) return 1;
+    return hipeig_spmv_shift_pair(c, A, zr[0], zi[0], sign, c->blk_ws, c->blk_ws + half, Yre[0], Yim[0]);
+  }
   if (npairs == 1 || c->collectives) {
     for (int p = 0; p < npairs; ++p)
       if (hipeig_spmv_shift_pair(c, A, zr[p * zstride], zi[p * zstride], sign, Xre[p], Xim[p], Yre[p], Yim[p])) return 1;
@@ -395,7 +476,8 @@ static int spmm_shift_pairs_impl(hipeig_ctx* c, hipeig_csr* A, int npairs, const
       cols[2 * p] = Xre[p0 + p]; cols[2 * p + 1] = Xim[p0 + p];
       outs[2 * p] = Yre[p0 + p]; outs[2 * p + 1] = Yim[p0 + p];
     }
-    if (hipeig_block_pack(c, K, nx, 2 * np, cols, Xi)) return 1;
+    if (Mre ? block_pack_scaled(c, K, nx, 2 * np, cols, nullptr, Mre + p0, Mim + p0, Xi)
+            : hipeig_block_pack(c, K, nx, 2 * np, cols, Xi)) return 1;
     int rc;
     if (zstride == 0) {
       const double ar = sign * zr[0], ai = sign * zi[0];
@@ -423,6 +505,48 @@ extern "C" int hipeig_spmm_shift_pairs(hipeig_ctx* c, hipeig_csr* A, int npairs,
 extern "C" int hipeig_spmm_shift_pairs_z(hipeig_ctx* c, hipeig_csr* A, int npairs, const double* zr, const double* zi, double sign,
                                          const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim) {
   return spmm_shift_pairs_impl(c, A, npairs, zr, zi, 1, sign, Xre, Xim, Yre, Yim);
+}
+
+// ---- the products of the diagonally right-preconditioned GCROT solves (gcrot_precond.hip) -----------------
+static int whole_operator_without_collectives(const hipeig_ctx* c, const hipeig_csr* A) {
+  HIPEIG_REQUIRE(!c->collectives, "the preconditioned GCROT products run on one GPU: a context with collectives is not implemented");
+  HIPEIG_REQUIRE(A->nrows == A->ncols && A->row_offset == 0, "the preconditioned GCROT products need a whole square operator");
+  return 0;
+}
+
+// hipeig_spmm_shift on T_j = minv (.) X_j: Y_j = sign*(sigma*T_j - H T_j), T_j formed while the operands are packed.  The
+// chunking, the sweep and ShiftBlockEpilogue are hipeig_spmm_shift's.
+extern "C" int hipeig_spmm_shift_m(hipeig_ctx* c, hipeig_csr* A, int k, double sigma, double sign, const double* minv,
+                                   const double* const* X, double* const* Y) {
+  HIPEIG_REQUIRE(k >= 1 && minv && X && Y, "bad arguments");
+  HIPEIG_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
+  if (whole_operator_without_collectives(c, A)) return 1;
+  if (A->nrows == 0) return 0;
+  const int64_t n = A->nrows;
+  if (ensure_blk_ws(c, (size_t)(2 * n) * BCOO_KMAX)) return 1;
+  double* Xi = c->blk_ws;
+  double* Yi = c->blk_ws + (size_t)n * BCOO_KMAX;
+  const double a_self = sign * sigma, a_sum = -sign;
+  for (int j0 = 0; j0 < k;) {
+    const int K = (k - j0 <= 4) ? 4 : 8;
+    const int kk = (k - j0 < K) ? k - j0 : K;
+    if (block_pack_scaled(c, K, n, kk, X + j0, minv, nullptr, nullptr, Xi)) return 1;
+    if (K == 4 ? spmm_block_run<4>(c, A, Xi, ShiftBlockEpilogue<4>{a_self, a_sum, Xi, Yi})
+               : spmm_block_run<8>(c, A, Xi, ShiftBlockEpilogue<8>{a_self, a_sum, Xi, Yi})) return 1;
+    if (hipeig_block_unpack(c, K, n, kk, Yi, Y + j0)) return 1;
+    j0 += kk;
+  }
+  return 0;
+}
+
+// hipeig_spmm_shift_pairs_z on t_p = Minv_p (.) x_p, a minv per operand: y_p = sign*(z_p*t_p - H t_p).
+extern "C" int hipeig_spmm_shift_pairs_zm(hipeig_ctx* c, hipeig_csr* A, int npairs, const double* zr, const double* zi, double sign,
+                                          const double* const* Mre, const double* const* Mim,
+                                          const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim) {
+  HIPEIG_REQUIRE(Mre && Mim, "bad arguments");
+  for (int p = 0; p < npairs; ++p) HIPEIG_REQUIRE(Mre[p] != nullptr, "every operand needs the real half of its minv");
+  if (whole_operator_without_collectives(c, A)) return 1;
+  return spmm_shift_pairs_impl(c, A, npairs, zr, zi, 1, sign, Xre, Xim, Yre, Yim, Mre, Mim);
 }
 
 extern "C" int hipeig_csr_block_info(hipeig_csr* A, int64_t info[4]) {

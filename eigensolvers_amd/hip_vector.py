@@ -67,8 +67,41 @@ def _preconditioner(o, sigma=None, x0=None, ctx=None):
     return pre
 
 
+def _gcrot_preconditioner(o, x0=None, ctx=None, H=None):
+    """``o["gcrotPreconditioner"]`` of a ``linearSystemArgs`` dict, validated: ``None`` or ``"jacobi"``, the diagonal RIGHT
+    preconditioner of the GCROT solves (``HipVector.solve``).  A key of its own: ``"preconditioner"`` belongs to MINRES and
+    keeps its refusals.  Returns ``None`` or the relative floor (``o["preconditionerFloor"]``) as a float."""
+    pre = o.get("gcrotPreconditioner")
+    if pre is None:
+        return None
+    if pre != "jacobi":
+        raise ValueError(f'linearSystemArgs["gcrotPreconditioner"] must be None or "jacobi", got {pre!r}')
+    name = o["linearSolver"]
+    if name != "gcrotmk":
+        raise ValueError(f'linearSystemArgs["gcrotPreconditioner"] is honoured by linearSolver="gcrotmk" only, not {name!r}')
+    floor = o.get("preconditionerFloor", PRECONDITIONER_FLOOR_DEFAULT)
+    if not (isinstance(floor, (int, float, np.floating, np.integer)) and 0.0 <= float(floor) < float("inf")):
+        raise ValueError(f'linearSystemArgs["preconditionerFloor"] must be a finite number >= 0, got {floor!r}')
+    if x0 is not None:
+        raise NotImplementedError("the preconditioned GCROT starts from x = 0: an initial guess (x0) is not implemented "
+                                  "with a preconditioner")
+    if ctx is not None and (ctx.collectives or ctx.direct_only):
+        raise NotImplementedError("the preconditioned GCROT runs on one GPU: a context with collectives (a row partition, "
+                                  "or its HIPEIG_FORCE_COLLECTIVES rehearsal) or a direct-only communicator is not "
+                                  "implemented")
+    if H is not None and not (isinstance(H, HipCsrOperator) and H.nrows == H.ncols and H.row_offset == 0):
+        raise NotImplementedError("the preconditioned GCROT needs a whole HipCsrOperator (nrows == ncols, row_offset == 0): "
+                                  "its diagonal is the preconditioner")
+    return float(floor)
+
+
 def _ptr_table(bufs):
     arr = (C.c_void_p * len(bufs))(*[b.ptr for b in bufs])
+    return C.cast(arr, C.POINTER(C.c_void_p)), arr
+
+
+def _ptr_table_or_null(bufs):
+    arr = (C.c_void_p * len(bufs))(*[None if b is None else b.ptr for b in bufs])
     return C.cast(arr, C.POINTER(C.c_void_p)), arr
 
 
@@ -355,6 +388,39 @@ class HipCsrOperator:
         self._jacobi = (key, minv)
         return minv
 
+    JACOBI_Z_CACHE = 16      # entries (16 n bytes each) of jacobi_inverse_z's cache: the contour points of a FEAST run recur
+                             # every iteration, and a pool holds at most gcrotmk.POOL_MAX_WIDTH = 16 of them at once
+
+    def jacobi_inverse_z(self, z, floor=PRECONDITIONER_FLOOR_DEFAULT):
+        """``(minv_re, minv_im)`` device buffers of GCROT's diagonal right preconditioner ``M^-1 = diag(1 / (z - d_i))`` for
+        a real shift or a complex contour point ``z``, kept away from ``d_i == z`` by the relative ``floor``
+        (``hipeig_jacobi_inverse_z``; ``precond_gcrotmk.jacobi_inverse_z_host`` is its NumPy statement).  ``minv_im`` is
+        ``None`` for a real ``z``.  Unlike ``jacobi_inverse`` it keeps sign and phase.  The latest ``JACOBI_Z_CACHE``
+        ``(complex(z), floor)`` are kept, least recently used dropped first.  ``ValueError`` where an element would not be
+        finite (``d_i == z`` with ``floor = 0``), ``d`` is not finite or every ``|z - d_i|`` is 0."""
+        if not (self.nrows == self.ncols and self.row_offset == 0):
+            raise NotImplementedError("jacobi_inverse_z needs a whole operator (nrows == ncols, row_offset == 0)")
+        z = complex(z)
+        key = (z, float(floor))
+        cache = self.__dict__.setdefault("_jacobi_z", {})
+        if key in cache:
+            cache[key] = cache.pop(key)                  # most recently used last
+            return cache[key]
+        d = self.diagonal()
+        re = self.ctx.alloc(self.nrows)
+        im = self.ctx.alloc(self.nrows) if z.imag != 0.0 else None
+        try:
+            _lib.call("hipeig_jacobi_inverse_z", self.ctx.handle, self.nrows, d.ptr, z.real, z.imag, key[1], re.ptr,
+                      None if im is None else im.ptr)
+        except _lib.HipEigError as exc:
+            if "not finite" in str(exc):
+                raise ValueError(str(exc)) from None
+            raise
+        while len(cache) >= self.JACOBI_Z_CACHE:
+            del cache[next(iter(cache))]
+        cache[key] = (re, im)
+        return cache[key]
+
     VARIANTS = {0: "none", 1: "csr-vector", 2: "csr-stream", 3: "column-window-blocked(wave)",
                 4: "column-window-blocked(workgroup)", 5: "column-window-blocked(workgroup, fixed-point)"}
 
@@ -521,6 +587,57 @@ class HipCsrOperator:
             return ys
         _lib.call("hipeig_spmm_shift_pairs", self.ctx.handle, self.handle, len(xs), z.real, z.imag, -1.0 if reverse else 1.0,
                   t_xr, t_xi, t_yr, t_yi)
+        return ys
+
+    # ---- products of the diagonally right-preconditioned GCROT solves: the same with minv (.) x in place of x --------------
+    def diag_mul(self, minv, x, y=None):
+        """``y = minv (.) x`` for a real ``x`` (a DeviceBuffer) or a complex one (a ``(re, im)`` pair) and a ``minv`` as
+        ``jacobi_inverse_z`` returns it; a real ``x`` needs a real ``minv``.  ``y``: where to (may be ``x``), default new
+        buffers.  Returns ``y``."""
+        n = self.nrows
+        if isinstance(x, tuple):
+            y = (self.ctx.alloc(n), self.ctx.alloc(n)) if y is None else y
+            _lib.call("hipeig_pair_diag_mul", self.ctx.handle, n, minv[0].ptr, None if minv[1] is None else minv[1].ptr,
+                      x[0].ptr, x[1].ptr, y[0].ptr, y[1].ptr)
+            return y
+        if minv[1] is not None:
+            raise ValueError("a real operand takes a real minv")
+        y = self.ctx.alloc(n) if y is None else y
+        _lib.call("hipeig_diag_mul", self.ctx.handle, n, minv[0].ptr, x.ptr, y.ptr)
+        return y
+
+    def apply_shifted_m(self, sigma, minv, x, y, reverse=False):
+        """``y = sign*(sigma*t - H t)``, ``t = minv (.) x``: one scaling, then ``apply_shifted``."""
+        self.apply_shifted(sigma, self.diag_mul(minv, x), y, reverse=reverse)
+
+    def apply_shifted_block_m(self, sigma, minv, xs, reverse=False):
+        """``apply_shifted_block`` on ``minv (.) x``, scaled while the operands are packed (``hipeig_spmm_shift_m``)."""
+        ys = [self.ctx.alloc(self.nrows) for _ in xs]
+        xt, keep1 = _ptr_table(xs)
+        yt, keep2 = _ptr_table(ys)
+        _lib.call("hipeig_spmm_shift_m", self.ctx.handle, self.handle, len(xs), float(sigma), -1.0 if reverse else 1.0,
+                  minv[0].ptr, xt, yt)
+        return ys
+
+    def apply_shifted_pairs_m(self, zs, minvs, xs, reverse=False):
+        """``apply_shifted_pairs`` with a shift AND a ``minv`` per operand, ``[sign*(z_p*t_p - H t_p)]`` with
+        ``t_p = minv_p (.) x_p`` scaled while the operands are packed (``hipeig_spmm_shift_pairs_zm``); one operand is one
+        scaling and the single pair product."""
+        zs = np.asarray(zs, dtype=np.complex128).reshape(-1)
+        if not (len(zs) == len(xs) == len(minvs)):
+            raise ValueError(f"{len(zs)} shifts and {len(minvs)} minv for {len(xs)} operands")
+        n = self.nrows
+        ys = [(self.ctx.alloc(n), self.ctx.alloc(n)) for _ in xs]
+        t_mr, k0 = _ptr_table([m[0] for m in minvs])
+        t_mi, k00 = _ptr_table_or_null([m[1] for m in minvs])
+        t_xr, k1 = _ptr_table([x[0] for x in xs])
+        t_xi, k2 = _ptr_table([x[1] for x in xs])
+        t_yr, k3 = _ptr_table([y[0] for y in ys])
+        t_yi, k4 = _ptr_table([y[1] for y in ys])
+        zr, zi = np.ascontiguousarray(zs.real), np.ascontiguousarray(zs.imag)
+        DP = C.POINTER(C.c_double)
+        _lib.call("hipeig_spmm_shift_pairs_zm", self.ctx.handle, self.handle, len(xs), zr.ctypes.data_as(DP),
+                  zi.ctypes.data_as(DP), -1.0 if reverse else 1.0, t_mr, t_mi, t_xr, t_xi, t_yr, t_yi)
         return ys
 
     def apply_pair(self, xr, xi, yr, yi):
@@ -738,10 +855,20 @@ class HipVector(AbstractVector):
         PRECONDITIONED quantities - ``beta1 = sqrt(<b, M^-1 b>)`` and the residual estimate ``phibar`` in the ``M^-1`` norm,
         exactly what ``scipy.sparse.linalg.minres(A, b, M=...)`` does - so the 2-norm residual at the stop is not the plain
         solve's.  ``last_solve_stats`` keeps its keys and gains ``"preconditioner": "jacobi"``.  It pays on diagonally
-        dominant operators and buys nothing on others."""
+        dominant operators and buys nothing on others.
+
+        ``linearSystemArgs["gcrotPreconditioner"] = "jacobi"`` (default ``None``; with ``linearSolver="gcrotmk"``, no
+        ``x0``, one GPU, a whole operator - anything else raises) is the key of the GCROT solves, real shift or complex
+        contour point ``z``, here and in every lock-step form of ``solveBlock``: SciPy's ``gcrotmk(A, b, M=...)`` with the
+        diagonal ``M = diag(1 / (z - h_ii))``, kept away from ``h_ii == z`` by the same relative
+        ``"preconditionerFloor"`` (``HipCsrOperator.jacobi_inverse_z``).  SciPy applies ``M`` on the right, so the
+        unchanged solver runs on ``sign (z I - H) M`` and its result ``u`` is returned as ``x = M u``; the residual it
+        tests is the true one, so ``linear_tol`` and ``linear_atol`` keep their meaning.  ``last_solve_stats`` gains
+        ``"preconditioner": "jacobi"``.  DESIGN.md 3.4b says where it pays and where it does not."""
         if not isinstance(H, HipCsrOperator):
             raise TypeError("HipVector.solve needs a HipCsrOperator (device-resident CSR)")
         pre = _preconditioner(b.options["linearSystemArgs"], sigma, x0, b.ctx)
+        gfloor = _gcrot_preconditioner(b.options["linearSystemArgs"], x0, b.ctx, H)
         if isinstance(b, HipComplexVector):                 # HipVector(complex array) is a HipComplexVector: same entry point
             return HipComplexVector.solve(H, b, sigma, x0, opType, reverseGF)
         if b.options["linearSystemArgs"]["linearSolver"] == "minres_shifted":
@@ -766,18 +893,26 @@ class HipVector(AbstractVector):
         if name == "gcrotmk":
             # numpyVector.py:161: gcrotmk(linOp, b, x0, tol, atol, maxiter) with SciPy's m = k = 20
             from .gcrotmk import gcrotmk_device
+            minv = None if gfloor is None else H.jacobi_inverse_z(float(sigma), gfloor)
 
             def matvec(buf):
                 out = b.ctx.alloc(b._buf.n)
-                H.apply_shifted(sigma, buf, out, reverse=reverseGF)
+                if minv is not None:                        # SciPy's right preconditioner: w = A (M v)
+                    H.apply_shifted_m(sigma, minv, buf, out, reverse=reverseGF)
+                else:
+                    H.apply_shifted(sigma, buf, out, reverse=reverseGF)
                 return out
 
             xbuf, conv, gstats = gcrotmk_device(b.ctx, matvec, b._buf, b._buf.n, rtol=float(o["linear_tol"]),
                                                 atol=float(o["linear_atol"]), maxiter=int(o["linearIter"]),
                                                 x0=None if x0 is None else x0._buf,
                                                 cols_per_pass=int(o.get("arnoldiColumnsPerPass", 1)))
+            if minv is not None:
+                H.diag_mul(minv, xbuf, xbuf)                # x = M u
             res = b._new(xbuf)
             res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"]}
+            if minv is not None:
+                res.last_solve_stats["preconditioner"] = "jacobi"
             if conv != 0:
                 raise UserWarning("Warning:: Iterative solver is not converged ")
             return res
@@ -1012,8 +1147,12 @@ class HipVector(AbstractVector):
         from .gcrotmk import gcrotmk_device
         ctx, n = b.ctx, len(b)
         sgn = -1.0 if reverseGF else 1.0
+        gfloor = _gcrot_preconditioner(o, x0, ctx, H)
+        minv = None if gfloor is None else H.jacobi_inverse_z(z, gfloor)
 
         def matvec(v):                                  # sgn * ((zr + i zi)(vr + i vi) - H vr - i H vi)
+            if minv is not None:                        # SciPy's right preconditioner: w = A (M v)
+                return H.apply_shifted_pairs_m([z], [minv], [v], reverse=reverseGF)[0]
             out_r, out_i = ctx.alloc(n), ctx.alloc(n)
             H.apply_shifted_pair(z, v[0], v[1], out_r, out_i, reverse=reverseGF)
             return (out_r, out_i)
@@ -1039,8 +1178,12 @@ class HipVector(AbstractVector):
                                          atol=float(o["linear_atol"]), maxiter=int(o["linearIter"]),
                                          complex_pairs=True, x0=guess,
                                          cols_per_pass=int(o.get("arnoldiColumnsPerPass", 1)))
+        if minv is not None:
+            H.diag_mul(minv, x, x)                      # x = M u
         res = HipComplexVector(b._new(x[0]), b._new(x[1]))
         res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"]}
+        if minv is not None:
+            res.last_solve_stats["preconditioner"] = "jacobi"
         if conv != 0:
             raise UserWarning("Warning:: Iterative solver is not converged ")
         return res
@@ -1061,7 +1204,12 @@ class HipVector(AbstractVector):
             _lib.call("hipeig_vec_fill", ctx.handle, zero.ptr, n, 0.0)
             rhs.append((b._buf, zero))
 
+        gfloor = _gcrot_preconditioner(o, None, ctx, H)
+        minv = None if gfloor is None else H.jacobi_inverse_z(z, gfloor)
+
         def block_matvec(vs):
+            if minv is not None:
+                return H.apply_shifted_pairs_m([z] * len(vs), [minv] * len(vs), vs, reverse=reverseGF)
             return H.apply_shifted_pairs(z, vs, reverse=reverseGF)
 
         sols = gcrotmk_device_block(ctx, block_matvec, rhs, n, rtol=float(o["linear_tol"]), atol=float(o["linear_atol"]),
@@ -1069,8 +1217,12 @@ class HipVector(AbstractVector):
                                     cols_per_pass=int(o.get("arnoldiColumnsPerPass", 1)))
         out, failed = [], False
         for b, (x, conv, gstats) in zip(bs, sols):
+            if minv is not None:
+                H.diag_mul(minv, x, x)
             res = HipComplexVector(b._new(x[0]), b._new(x[1]))
             res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"]}
+            if minv is not None:
+                res.last_solve_stats["preconditioner"] = "jacobi"
             failed = failed or conv != 0
             out.append(res)
         if failed:
@@ -1100,7 +1252,10 @@ class HipVector(AbstractVector):
     # Device memory one complex GCROT(m, k) solve keeps alive, in complex vectors (16 n bytes each): the iterate and the
     # residual (2), c outer pairs (2c) and the Arnoldi vectors of a cycle of m + (k - c) steps (m + k - c + 1), largest with
     # the recycle space full (c = k): 2k + m + 1; plus the new pair (ux, cx), the product just returned and the operand of
-    # a complex scaling while they are being built (4).  SciPy's m = k = 20: 67 vectors, 1072 n bytes.
+    # a complex scaling while they are being built (4).  SciPy's m = k = 20: 67 vectors, 1072 n bytes.  With
+    # linearSystemArgs["gcrotPreconditioner"] the pool also holds one Minv per distinct contour point (16 n bytes each, the
+    # HipCsrOperator.JACOBI_Z_CACHE latest stay with the operator): they belong to the call, not to a solve, and are built
+    # before _pool_width reads the free memory, so its estimate has already paid for them.
     @staticmethod
     def _pool_vectors_per_solve(m=20, k=20):
         return 2 + (2 * k + m + 1) + 4
@@ -1131,7 +1286,13 @@ class HipVector(AbstractVector):
         zero = ctx.alloc(n)                              # the right-hand sides are real and only read: one zero half for all
         _lib.call("hipeig_vec_fill", ctx.handle, zero.ptr, n, 0.0)
 
+        gfloor = _gcrot_preconditioner(o, None, ctx, H)
+        # a minv per contour point, built before _pool_width reads the free memory so that its estimate sees them
+        minvs = None if gfloor is None else {z: H.jacobi_inverse_z(z, gfloor) for z in dict.fromkeys(zs)}
+
         def block_matvec(vs, tags):
+            if minvs is not None:
+                return H.apply_shifted_pairs_m([zs[t] for t in tags], [minvs[zs[t]] for t in tags], vs, reverse=reverseGF)
             return H.apply_shifted_pairs([zs[t] for t in tags], vs, reverse=reverseGF)
 
         pool = poolStats if poolStats is not None else {}
@@ -1141,8 +1302,12 @@ class HipVector(AbstractVector):
                 rtol=float(o["linear_tol"]), atol=float(o["linear_atol"]), maxiter=int(o["linearIter"]),
                 complex_pairs=True, cols_per_pass=int(o.get("arnoldiColumnsPerPass", 1)), pool_stats=pool):
             b = bs[i]
+            if minvs is not None:
+                H.diag_mul(minvs[zs[i]], x, x)
             res = HipComplexVector(b._new(x[0]), b._new(x[1]))
             res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"]}
+            if minvs is not None:
+                res.last_solve_stats["preconditioner"] = "jacobi"
             failed = failed or conv != 0
             if onSolution is not None:
                 onSolution(i, res)
@@ -1165,7 +1330,12 @@ class HipVector(AbstractVector):
         ctx, n = bs[0].ctx, bs[0]._buf.n
         H.honour_reduction_option(bs[0].options)
 
+        gfloor = _gcrot_preconditioner(o, None, ctx, H)
+        minv = None if gfloor is None else H.jacobi_inverse_z(sigma, gfloor)
+
         def block_matvec(vs):
+            if minv is not None:
+                return H.apply_shifted_block_m(sigma, minv, vs, reverse=reverseGF)
             return H.apply_shifted_block(sigma, vs, reverse=reverseGF)
 
         sols = gcrotmk_device_block(ctx, block_matvec, [b._buf for b in bs], n, rtol=float(o["linear_tol"]),
@@ -1173,9 +1343,13 @@ class HipVector(AbstractVector):
                                     cols_per_pass=int(o.get("arnoldiColumnsPerPass", 1)))
         out, failed = [], False
         for b, (x, conv, gstats) in zip(bs, sols):
+            if minv is not None:
+                H.diag_mul(minv, x, x)
             res = b._new(x)
             res.last_solve_stats = b.last_solve_stats = {"iterations": gstats["matvecs"], "outer": gstats["outer"],
                                                          "lock_step": True}
+            if minv is not None:
+                res.last_solve_stats["preconditioner"] = "jacobi"
             failed = failed or conv != 0
             out.append(res)
         if failed:
@@ -1388,6 +1562,7 @@ class HipComplexVector(AbstractVector):
             raise TypeError("HipComplexVector.solve needs a HipCsrOperator (device-resident CSR)")
         o = b.options["linearSystemArgs"]
         _preconditioner(o, sigma, x0, b.ctx)
+        _gcrot_preconditioner(o, x0, b.ctx, H)
         if o["linearSolver"] == "minres_shifted":
             raise NotImplementedError("linearSolver='minres_shifted' takes a real right-hand side (its Lanczos run is real)")
         if o["linearSolver"] == "pardiso":

@@ -276,6 +276,39 @@ int hipeig_spmm_shift_pairs(hipeig_ctx* ctx, hipeig_csr* A, int npairs, double z
  * roundings per element.                                                                                              */
 int hipeig_spmm_shift_pairs_z(hipeig_ctx* ctx, hipeig_csr* A, int npairs, const double* zr, const double* zi, double sign,
                               const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim);
+
+/* ---- diagonal right preconditioner of GCROT(m,k) (opt-in: linearSystemArgs["gcrotPreconditioner"] = "jacobi") ---- */
+/* The reference calls scipy.sparse.linalg.gcrotmk without M (numpyVector.py:161; feast.py:83-90 for the contour points), so
+ * these restate SciPy 1.15.3, not the reference: gcrotmk(A, b, M=diags(minv)) applies M on the right (_fgmres: z = M v,
+ * w = A z), i.e. it is gcrotmk on the composed operator v -> A (minv (.) v) followed by x = minv (.) u.
+ *
+ * minv = 1 / (z - d[i]) for z = zr + i zi, kept away from a diagonal entry that meets z: with m_i = z - d[i], t_i = |m_i|
+ * and g = floor_rel * max_j t_j it is 1 / m_i where t_i >= g, the phase of 1 / m_i at modulus 1 / g where 0 < t_i < g and
+ * 1 / g where t_i == 0.  Unlike hipeig_jacobi_inverse it keeps sign and phase: GCROT needs no positive definite M.
+ * zi == 0: a real minv, minv_im may be NULL (zeros are written when it is not); else minv_im is required.  Fails
+ * (hipeig_last_error, "not finite") before anything is written when an element would not be finite (a d[i] equal to z
+ * with floor_rel = 0), when d holds a non-finite value or when every t_i is 0.                                          */
+int hipeig_jacobi_inverse_z(hipeig_ctx* ctx, int64_t n, const double* d, double zr, double zi, double floor_rel,
+                            double* minv_re, double* minv_im);
+/* y = m (.) x, element by element: SciPy's `M v` for M = diags(m) (and the closing x = M u).  y may be x.  Asynchronous. */
+int hipeig_diag_mul(hipeig_ctx* ctx, int64_t n, const double* m, const double* x, double* y);
+/* The same for complex x = xr + i xi and m = mr + i mi; mi == NULL: a real m.  (yr, yi) may be (xr, xi).               */
+int hipeig_pair_diag_mul(hipeig_ctx* ctx, int64_t n, const double* mr, const double* mi, const double* xr, const double* xi,
+                         double* yr, double* yi);
+/* hipeig_spmm_shift (above) applied to T[j] = minv (.) X[j] - SciPy's w = A (M v) for the lock-step real-shift solves:
+ * Y[j] = sign*(sigma*T[j] - H T[j]), T[j] formed with hipeig_diag_mul's element while the operands are packed, so the
+ * result is hipeig_spmm_shift's on hipeig_diag_mul's output.  A whole square operator on a context without collectives. */
+int hipeig_spmm_shift_m(hipeig_ctx* ctx, hipeig_csr* A, int k, double sigma, double sign, const double* minv,
+                        const double* const* X, double* const* Y);
+/* hipeig_spmm_shift_pairs_z (above) applied to t_p = Minv_p (.) x_p with a minv PER OPERAND (Mre[p], Mim[p]; Mim[p] may
+ * be NULL), so that operands of different contour points still share a pass over the operator: Y_p = sign*(z_p*t_p - H t_p),
+ * t_p formed with hipeig_pair_diag_mul's element while the operands are packed.  Chunking, width rule and sweeps are those
+ * of hipeig_spmm_shift_pairs_z; npairs == 1 is hipeig_pair_diag_mul, then hipeig_spmv_shift_pair.  A whole square
+ * operator on a context without collectives.                                                                          */
+int hipeig_spmm_shift_pairs_zm(hipeig_ctx* ctx, hipeig_csr* A, int npairs, const double* zr, const double* zi, double sign,
+                               const double* const* Mre, const double* const* Mim,
+                               const double* const* Xre, const double* const* Xim, double* const* Yre, double* const* Yim);
+
 /* Kernel choice of the block product / block solve: 0 = automatic, 1 = row-owner CSR (a wavefront per row,
  * 64-byte gathers from wherever the operand block lives), 2 = column-window blocked (operand windows
  * L2-resident, 8 accumulators per row in LDS).  info[0] = variant of the last block launch, [1] = row
