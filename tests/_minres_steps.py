@@ -15,6 +15,16 @@ measured do; it is held to ``8 D``, the factor of the Lanczos filter's rotation 
 
 ``fault`` plants the one-line faults the CPU test must see exceed ``8 D`` (``FAULTS``).
 
+The row-partitioned solves (``test_gpu_partitioned_steps.py``) are read further: they enqueue chunks of 16 iterations with
+no flush between two chunks, so what can go wrong there - a pending iterate update lost at a boundary, a share of ``<y,y>``
+missing at one step - does not exist within four steps.  On the well-conditioned g1037 / g20001 systems the ``longdouble``
+run can still be held at ``LONG_STEPS``: 16 ends at a chunk boundary, 17 and 18 carry one pending update across it, 32 ends
+at the second boundary, 33 crosses two.  ``D_LONG`` is ``D``'s definition over ``LONG_CASES`` x ``LONG_STEPS``, with the
+orders joined by ``Double("slabs", P)`` - the sum in rank order of the ranks' own sums, as the loopback all-reduce adds; a
+device run is held to ``8 D_LONG`` there, by the reasoning of ``8 D``.  The small systems (n = 63, 64, 65) nearly exhaust
+their Krylov space by step 34 (the orders disagree by 5e3 .. 1e6 u): they are read over K steps only.  ``LONG_FAULTS`` are
+the faults of that path; two of them pass at steps 1 .. 4, which is why four steps are not enough.
+
 The exit cases (``EXITS``) are operators on which the oracle stops with the rare codes by a factor of 2 at least
 (``exit_margin``), so that device rounding cannot move the step.
 """
@@ -24,6 +34,7 @@ import numpy as np
 import scipy.sparse as sp
 
 import _hiprec as hp
+from eigensolvers_amd.distributed import row_range
 from eigensolvers_amd.generators import gapped_csr_host
 from eigensolvers_amd.precond_minres import csr_diagonal_host, jacobi_inverse_host
 
@@ -35,7 +46,12 @@ STATS = ("rnorm", "Anorm", "ynorm", "test1", "test2", "Acond")
 D = 13.0                         # in u: measured_deviation over CASES gives 12.84 (EXPERIMENTS.md); the condition on the table is D <= 16
 FACTOR = 8
 ORDERS = ("dot", "pairwise", "reversed", "fsum")
-FAULTS = ("swap_w", "c1_inverted", "kc_tail", "phi_old", "alfa_f32", "dbar_sign", "z_prev", "ynorm_no_x0")
+K_FAULTS = ("swap_w", "c1_inverted", "kc_tail", "phi_old", "alfa_f32", "dbar_sign", "z_prev", "ynorm_no_x0")
+LONG_FAULTS = ("ynorm_lagged", "kd_dropped_at_16", "yy_share_missing")     # of the row-partitioned path, seen at LONG_STEPS
+FAULTS = K_FAULTS + LONG_FAULTS
+LONG_STEPS = (1, 2, 3, 4, 16, 17, 18, 32, 33)
+LONG_ORDERS = ORDERS + (("slabs", 2), ("slabs", 3))
+D_LONG = 23.0                   # in u: measured_long_deviation gives 22.83 (EXPERIMENTS.md); the condition on the table is D_LONG <= 32
 
 
 # ---------------------------------------------------------------- operators
@@ -85,18 +101,25 @@ class Wide:
 
 
 class Double:
-    """float64 with the inner products summed in ``order``; the product is scipy's (a row's terms in stored order)."""
+    """float64 with the inner products summed in ``order``; the product is scipy's (a row's terms in stored order).
+    ``Double("slabs", P)``: the sum, in rank order, of ``np.dot`` over the ``row_range`` slabs of P ranks."""
     real = np.float64
 
-    def __init__(self, order="dot"):
-        assert order in ORDERS
-        self.name = order
+    def __init__(self, order="dot", P=None):
+        assert order in ORDERS or (order == "slabs" and P >= 1)
+        self.name, self.P = order, P
 
     @staticmethod
     def matvec(op, v):
         return op.A @ v
 
     def dot(self, x, y):
+        if self.name == "slabs":
+            acc = np.float64(0.0)
+            for r in range(self.P):
+                lo, hi = row_range(len(x), self.P, r)
+                acc = acc + np.float64(np.dot(x[lo:hi], y[lo:hi]))
+            return acc
         if self.name == "dot":
             return np.float64(np.dot(x, y))
         if self.name == "pairwise":
@@ -159,7 +182,11 @@ def steps(op, b, sigma, sign, nsteps, arith, minv=None, x0=None, fault=None):
             zprev = z
             z = r2 if mv is None else mv * r2
             oldb = beta
-            beta = sqrt(abs(arith.dot(r2, zprev))) if fault == "z_prev" else sqrt(arith.dot(r2, z))
+            if fault == "yy_share_missing" and itn == 17:              # the third of three slabs never arrived
+                cut = row_range(op.n, 3, 1)[1]
+                beta = sqrt(arith.dot(r2[:cut], z[:cut]))
+            else:
+                beta = sqrt(abs(arith.dot(r2, zprev))) if fault == "z_prev" else sqrt(arith.dot(r2, z))
             tnorm2 = tnorm2 + (alfa * alfa + oldb * oldb + beta * beta)
 
             oldeps = epsln
@@ -183,13 +210,15 @@ def steps(op, b, sigma, sign, nsteps, arith, minv=None, x0=None, fault=None):
                 w = (v - oldeps * w2 - delta * w1) * denom
             else:
                 w = (v - oldeps * w1 - delta * w2) * denom
-            x = x + phi * w
+            xlag = x
+            if not (fault == "kd_dropped_at_16" and itn == 16):
+                x = x + phi * w
 
             gmax = max(gmax, gamma)
             gmin = min(gmin, gamma)
 
             Anorm = sqrt(tnorm2)
-            xn = (x - xstart) if fault == "ynorm_no_x0" else x
+            xn = (x - xstart) if fault == "ynorm_no_x0" else xlag if fault == "ynorm_lagged" else x
             ynorm = sqrt(arith.dot(xn, xn))
             rnorm = phibar
             out.append(dict(x=x.copy(), alfa=alfa, beta=beta, rnorm=rnorm, Anorm=Anorm, ynorm=ynorm,
@@ -322,6 +351,7 @@ def _cases():
 
 
 CASES = _cases()
+LONG_CASES = ("g1037 sigma=0.02 sign=+1", "g1037 sigma=0.02 sign=-1", "g1037 x0", "g20001") + tuple(f"g1037 column {j}" for j in range(1, 8))
 
 
 def block_cases(k, jacobi=False):
@@ -333,22 +363,27 @@ def block_cases(k, jacobi=False):
 _refs = {}
 
 
-def reference(case, minv=None):
+def reference(case, minv=None, nsteps=None):
     """The ``longdouble`` run of a case, computed once and left unchanged.  ``minv``: the device's own inverse diagonal in
-    place of the host statement's (keyed by its bytes)."""
+    place of the host statement's (keyed by its bytes).  ``nsteps``: that many steps instead of ``case.nsteps`` (a case of
+    ``LONG_CASES`` is run to the last of ``LONG_STEPS`` the first time, so no record is ever computed twice)."""
     if not hp.EXTENDED:
         raise RuntimeError("longdouble is no wider than double here")
     mv = case.minv if minv is None else minv
     key = (case.name, None if minv is None else minv.tobytes())
-    if key not in _refs:
-        _refs[key] = steps(case.op, case.b, case.sigma, case.sign, case.nsteps, Wide, minv=mv, x0=case.x0)
+    want = case.nsteps if nsteps is None else nsteps
+    if key not in _refs or len(_refs[key]) < want:
+        run = max(want, LONG_STEPS[-1]) if case.name in LONG_CASES else want
+        _refs[key] = steps(case.op, case.b, case.sigma, case.sign, run, Wide, minv=mv, x0=case.x0)
         for rec in _refs[key]:
             rec["x"].setflags(write=False)
-    return _refs[key]
+    return _refs[key][:want]
 
 
-def run_double(case, order="dot", fault=None):
-    return steps(case.op, case.b, case.sigma, case.sign, case.nsteps, Double(order), minv=case.minv, x0=case.x0, fault=fault)
+def run_double(case, order="dot", fault=None, nsteps=None):
+    """``order``: one of ``ORDERS``, or ``("slabs", P)``."""
+    arith = Double(*order) if isinstance(order, tuple) else Double(order)
+    return steps(case.op, case.b, case.sigma, case.sign, nsteps or case.nsteps, arith, minv=case.minv, x0=case.x0, fault=fault)
 
 
 def measured_deviation(cases=None, stats=STATS[:5]):
@@ -363,6 +398,27 @@ def measured_deviation(cases=None, stats=STATS[:5]):
                 q = max(dev, key=dev.get)
                 table[(case.name, k, order)] = (dev[q], q)
     return max(v[0] for v in table.values()), table
+
+
+def measured_long_deviation(cases=None, stats=STATS[:5]):
+    """``measured_deviation`` over ``LONG_CASES`` (or ``cases``), the steps of ``LONG_STEPS`` and ``LONG_ORDERS``:
+    ``(D_LONG, table)``."""
+    table = {}
+    last = LONG_STEPS[-1]
+    for case in ([CASES[name] for name in LONG_CASES] if cases is None else cases):
+        ref = reference(case, nsteps=last)
+        for order in LONG_ORDERS:
+            got = run_double(case, order, nsteps=last)
+            for k in LONG_STEPS:
+                dev = step_deviations(got[k - 1], ref[k - 1], stats)
+                q = max(dev, key=dev.get)
+                table[(case.name, k, order if isinstance(order, str) else f"slabs of {order[1]}")] = (dev[q], q)
+    return max(v[0] for v in table.values()), table
+
+
+def step_bound(k):
+    """What a device record of step k is held to, in u: ``8 D`` over the first K steps, ``8 D_LONG`` after."""
+    return FACTOR * (D if k <= K else D_LONG)
 
 
 # ---------------------------------------------------------------- exits

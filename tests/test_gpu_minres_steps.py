@@ -35,17 +35,20 @@ def _record(x, st, k, info, n=None):
     return dict(x=x, rnorm=st[2], Anorm=st[3], ynorm=st[4], test1=st[5], test2=st[6], Acond=st[7])
 
 
-def single_steps(hip, H, case, entry="hipeig_minres", minv=None, nsteps=None):
-    """Records of steps 1 .. K of one of the single-vector entries on ``case``'s right-hand side."""
+def single_raw(hip, H, case, entry="hipeig_minres", minv=None, nsteps=None, rows=None, steps=None):
+    """``[(k, x_k, statistics, info, collectives)]`` of the runs to the steps asked for: the library calls and nothing else,
+    so that a rank of a group can make them (``rows = (lo, hi)``: the rank uploads its rows of ``b`` and ``x0`` and gets its
+    rows of ``x_k`` back; no check is made here, a rank that raised would leave its peers waiting in a collective)."""
     ctx = H.ctx
-    n = case.op.n
-    b = hip.HipVector(case.b.copy(), ctx=ctx)
-    x0 = hip.HipVector(case.x0.copy(), ctx=ctx) if entry == "hipeig_minres_x0" else None
+    lo, hi = rows or (0, case.op.n)
+    b = hip.HipVector(case.b[lo:hi].copy(), ctx=ctx)
+    x0 = hip.HipVector(case.x0[lo:hi].copy(), ctx=ctx) if entry == "hipeig_minres_x0" else None
     out = []
-    for k in range(1, (nsteps or case.nsteps) + 1):
-        xb = ctx.alloc(n)
+    for k in (steps or range(1, (nsteps or case.nsteps) + 1)):
+        xb = ctx.alloc(hi - lo)
         info = C.c_int(-1)
         st = (C.c_double * 8)()
+        cs = (C.c_int64 * 4)()
         head = (ctx.handle, H.handle, float(case.sigma), float(case.sign), b._buf.ptr)
         tail = (xb.ptr, 0.0, k, C.byref(info), st)
         if entry == "hipeig_minres":
@@ -54,57 +57,86 @@ def single_steps(hip, H, case, entry="hipeig_minres", minv=None, nsteps=None):
             _lib.call(entry, *head, x0._buf.ptr, *tail)
         else:
             _lib.call(entry, *head, minv.ptr, *tail)
-        out.append(_record(hip.HipVector(xb).array, st, k, info.value, n))
+        _lib.call("hipeig_comm_stats", ctx.handle, cs)
+        out.append((k, hip.HipVector(xb).array, list(st), info.value, int(cs[0])))
     return out
 
 
-def block_steps(hip, H, cols, sigma, sign, minv=None, nsteps=ms.K):
-    """``recs[j][k - 1]``: the record of step k of column j of the lock-step solve of ``cols`` (chunks of 8, as
-    ``solveBlock`` cuts them)."""
+def single_steps(hip, H, case, entry="hipeig_minres", minv=None, nsteps=None, rows=None, steps=None):
+    """Records of steps 1 .. K (or of ``steps``) of one of the single-vector entries on ``case``'s right-hand side."""
+    raw = single_raw(hip, H, case, entry, minv, nsteps, rows, steps)
+    return [_record(x, st, k, info, case.op.n) for k, x, st, info, _ in raw]
+
+
+def block_raw(hip, H, cols, sigma, sign, minv=None, nsteps=ms.K, rows=None, steps=None):
+    """``raw[j] = [(k, x_k, statistics, info, collectives)]`` of column j of the lock-step solve of ``cols`` (chunks of 8,
+    as ``solveBlock`` cuts them), read as ``single_raw`` reads: library calls only, ``rows`` the rank's rows."""
     ctx = H.ctx
-    n = len(cols[0])
-    recs = [[] for _ in cols]
+    lo, hi = rows or (0, len(cols[0]))
+    raw = [[] for _ in cols]
     for i0 in range(0, len(cols), 8):
-        chunk = [hip.HipVector(c.copy(), ctx=ctx) for c in cols[i0:i0 + 8]]
+        chunk = [hip.HipVector(c[lo:hi].copy(), ctx=ctx) for c in cols[i0:i0 + 8]]
         kc = len(chunk)
         bt, keep1 = _ptr_table([b._buf for b in chunk])
-        for k in range(1, nsteps + 1):
-            outs = [ctx.alloc(n) for _ in chunk]
+        for k in (steps or range(1, nsteps + 1)):
+            outs = [ctx.alloc(hi - lo) for _ in chunk]
             xt, keep2 = _ptr_table(outs)
             info = (C.c_int * kc)()
             st = (C.c_double * (8 * kc))()
+            cs = (C.c_int64 * 4)()
             if minv is None:
                 _lib.call("hipeig_minres_block", ctx.handle, H.handle, float(sigma), float(sign), kc, bt, xt, 0.0, k, info, st)
             else:
                 _lib.call("hipeig_minres_block_jacobi", ctx.handle, H.handle, float(sigma), float(sign), kc, bt, minv.ptr, xt,
                           0.0, k, info, st)
+            _lib.call("hipeig_comm_stats", ctx.handle, cs)
             for j in range(kc):
-                x = hip.HipVector(outs[j]).array
-                if not cols[i0 + j].any():                                  # a zero column: never started
-                    assert info[j] == 0 and not x.any() and st[8 * j] == 0
-                    recs[i0 + j].append(None)
-                else:
-                    recs[i0 + j].append(_record(x, st[8 * j:8 * j + 8], k, info[j]))
+                raw[i0 + j].append((k, hip.HipVector(outs[j]).array, list(st[8 * j:8 * j + 8]), info[j], int(cs[0])))
+    return raw
+
+
+def block_records(cols, raw):
+    """``recs[j][i]``: the record of the i-th step read of column j; a zero column was never started."""
+    recs = [[] for _ in cols]
+    for j, col in enumerate(cols):
+        for k, x, st, info, _ in raw[j]:
+            if not col.any():
+                assert info == 0 and not x.any() and st[0] == 0
+                recs[j].append(None)
+            else:
+                recs[j].append(_record(x, st, k, info))
     return recs
 
 
-def check_steps(label, case, recs, ref, x0=None):
-    """Every deviation of the records from the reference's is <= 8 D; prints the largest per quantity over the steps."""
+def block_steps(hip, H, cols, sigma, sign, minv=None, nsteps=ms.K, rows=None, steps=None):
+    """``recs[j][k - 1]``: the record of step k of column j of the lock-step solve of ``cols`` (chunks of 8, as
+    ``solveBlock`` cuts them)."""
+    return block_records(cols, block_raw(hip, H, cols, sigma, sign, minv, nsteps, rows, steps))
+
+
+def check_steps(label, case, recs, ref, x0=None, steps=None):
+    """Every deviation of the records from the reference's is <= 8 D (past step K, where ``steps`` lists the steps the
+    records were read at: <= 8 D_LONG); prints the largest ratio per quantity over the steps."""
     worst = {}
-    for k, (g, r) in enumerate(zip(recs, ref), start=1):
+    ks = list(steps) if steps else list(range(1, len(recs) + 1))
+    assert len(ks) == len(recs) and (steps is None or len(ref) >= ks[-1]), (label, ks, len(recs), len(ref))
+    for k, g in zip(ks, recs):
+        r = ref[k - 1]
+        bound = ms.step_bound(k) if steps else BOUND
         dev = ms.step_deviations(g, r, ms.STATS, case.scales(k, ref))
         if x0 is not None:
             # x_k - x0 carries the roundings of x_k itself, u ||x_k|| each: relative to ||x_k - x0|| that many times more
             dx = r["x"] - x0.astype(ms.LD)
             dev["x-x0"] = ms.deviation(g["x"].astype(ms.LD) - x0.astype(ms.LD), dx) / max(1.0, float(hp.nrm2(r["x"]) / hp.nrm2(dx)))
         for q, d in dev.items():
-            if d >= worst.get(q, (-1.0, 0))[0]:
-                worst[q] = (d, k)
-    print(f"STEPS {label}: largest deviation / (8 D = {BOUND:g} u): "
-          + ", ".join(f"{q} {d / BOUND:.3f} (step {k})" for q, (d, k) in worst.items()))
-    bad = {q: v for q, v in worst.items() if not v[0] <= BOUND}
+            if not d / bound < worst.get(q, (-1.0, 0))[0]:
+                worst[q] = (d / bound, k)
+    what = f"8 D = {BOUND:g} u" + (f", past step {ms.K} 8 D_LONG = {ms.FACTOR * ms.D_LONG:g} u" if steps and ks[-1] > ms.K else "")
+    print(f"STEPS {label}: largest deviation / ({what}): "
+          + ", ".join(f"{q} {d:.3f} (step {k})" for q, (d, k) in worst.items()))
+    bad = {q: v for q, v in worst.items() if not v[0] <= 1.0}
     assert not bad, (label, bad)
-    return max(d for d, _ in worst.values()) / BOUND
+    return max(d for d, _ in worst.values())
 
 
 _operators = {}

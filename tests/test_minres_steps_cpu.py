@@ -1,5 +1,6 @@
 """The reference of the MINRES step tests checked without a GPU (``_minres_steps.py``): its float64 form against the
-oracle, the NumPy twin and SciPy; the measured deviation ``D``; the planted faults; the margins of the exit cases."""
+oracle, the NumPy twin and SciPy; the measured deviations ``D`` and ``D_LONG``; the planted faults; the margins of the exit
+cases."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -91,7 +92,7 @@ def _applies(fault, case):
 
 
 @needs_extended
-@pytest.mark.parametrize("fault", ms.FAULTS)
+@pytest.mark.parametrize("fault", ms.K_FAULTS)
 def test_planted_fault_exceeds_8D(fault):
     """Every one-line fault is past ``8 D`` in some quantity at a step <= K on some case - and, for the faults that bear
     on a device configuration, on the case that configuration runs."""
@@ -113,6 +114,54 @@ def test_planted_fault_exceeds_8D(fault):
     for name in ("g1037 sigma=0.02 sign=+1", "g20001", "g1037 jacobi", "g1037 x0"):
         if name in seen:
             assert name in caught, (fault, name, seen[name])
+
+
+@needs_extended
+def test_no_summation_order_deviates_by_more_than_D_LONG_at_the_long_steps():
+    """``D_LONG``: ``D``'s definition over ``LONG_CASES`` and ``LONG_STEPS``, the four orders joined by the rank-ordered
+    slab sums of 2 and 3 ranks; ``Acond`` obeys it too."""
+    Dm, table = ms.measured_long_deviation(stats=ms.STATS)
+    worst = {}
+    for (name, k, order), (d, q) in table.items():
+        if d > worst.get(name, (0.0,))[0]:
+            worst[name] = (d, k, order, q)
+    for name, (d, k, order, q) in worst.items():
+        print(f"STEPS-CPU long {name}: {d:.2f} u ({q}, step {k}, {order})")
+    print(f"STEPS-CPU D_LONG measured {Dm:.2f} u, constant {ms.D_LONG}")
+    assert {k for _, k, _ in table} == set(ms.LONG_STEPS) and {n for n, _, _ in table} == set(ms.LONG_CASES)
+    assert Dm <= ms.D_LONG <= 32.0
+
+
+def test_slab_order_adds_the_ranks_sums_in_rank_order():
+    x = ms.rhs(1037)
+    y = ms.rhs(1037, 5)
+    for P in (2, 3):
+        acc = 0.0
+        for r in range(P):
+            lo, hi = ms.row_range(1037, P, r)
+            acc += float(np.dot(x[lo:hi], y[lo:hi]))
+        assert float(ms.Double("slabs", P).dot(x, y)) == acc
+    assert [ms.row_range(1037, 3, r) for r in range(3)] == [(0, 346), (346, 692), (692, 1037)]
+    assert float(ms.Double("slabs", 1).dot(x, y)) == float(np.dot(x, y))
+
+
+@needs_extended
+@pytest.mark.parametrize("fault", ms.LONG_FAULTS)
+def test_planted_long_fault_exceeds_8_D_LONG(fault):
+    """The faults of the row-partitioned path are past ``8 D_LONG`` at a step of ``LONG_STEPS`` on the case the group tests
+    run; a lost update at the chunk boundary and a missing share at step 17 stay within ``8 D`` over steps 1 .. 4 - four
+    steps cannot see them."""
+    case = ms.CASES["g1037 sigma=0.02 sign=+1"]
+    last = ms.LONG_STEPS[-1]
+    ref = ms.reference(case, nsteps=last)
+    got = ms.run_double(case, "dot", fault=fault, nsteps=last)
+    dev = {k: max(ms.step_deviations(got[k - 1], ref[k - 1], ms.STATS).values()) for k in ms.LONG_STEPS}
+    print(f"STEPS-CPU long fault {fault}: " + ", ".join(f"step {k}: {d:.3g} u" for k, d in dev.items()))
+    assert any(d > ms.step_bound(k) for k, d in dev.items() if k > ms.K), dev
+    if fault in ("kd_dropped_at_16", "yy_share_missing"):
+        assert all(dev[k] <= ms.FACTOR * ms.D for k in range(1, ms.K + 1)), dev
+    for k in ms.LONG_STEPS:
+        assert ms.step_bound(k) == ms.FACTOR * (ms.D if k <= ms.K else ms.D_LONG)
 
 
 def _twin_minv(e):
