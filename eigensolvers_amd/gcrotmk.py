@@ -305,7 +305,7 @@ def _gcrotmk(ops, ctx, b, n, rtol, atol, maxiter, m, k, complex_pairs, x0, stats
 
     if x0 is not None:                                 # SciPy: x = x0, r = b - A x0
         x = ops.copy(x0)
-        r = yield ("mv", x)
+        r = yield ("mv", mv(x))                        # counted like every other product
         ops.scal(-1.0, r)
         ops.axpy(1.0, b, r)
     else:
