@@ -526,7 +526,11 @@ int hipeig_csr_build_tcoo(hipeig_ctx* c, hipeig_csr* A) {
   if (rw > TCOO_MAX_RW) rw = TCOO_MAX_RW;
   if (const char* e = getenv("HIPEIG_TCOO_RW")) rw = (atoi(e) + 63) / 64 * 64;   // tuning knob
   HIPEIG_REQUIRE(rw >= 64 && rw * 32 <= 163840, "HIPEIG_TCOO_RW out of range");
-  if (rw > ((int64_t)1 << (32 - wbits))) rw = (int64_t)1 << (32 - wbits);
+  // (row_in_unit << wbits | col_in_window) must stay below 0xFFFFFFFF, the sweep's mark for "no entry": rw < 2^(32 - wbits),
+  // as spmm.hip keeps it for the block layout.  One step of 64 below, not 1: rw stays a multiple of 64, as the automatic
+  // choice and the knob round it (neither tcoo_build_kernel nor tcoo_sweep needs that; every wave's accumulators then
+  // start on a 512-byte boundary of the LDS).
+  if (rw >= ((int64_t)1 << (32 - wbits))) rw = ((int64_t)1 << (32 - wbits)) - 64;
   int per_cu = (int)(163840 / ((size_t)4 * rw * sizeof(double)));             // LDS-limited residency
   if (per_cu > 8) per_cu = 8;
   if (per_cu < 1) per_cu = 1;
@@ -736,7 +740,8 @@ static int build_tcoow_layout(hipeig_ctx* c, hipeig_csr* A, int pair) {
     }
   }
   if (const char* e = getenv(pair ? "HIPEIG_TCOOW_PAIR_RW" : "HIPEIG_TCOOW_RW")) rw = (atoi(e) + 63) / 64 * 64;   // tuning knob
-  HIPEIG_REQUIRE(rw >= 64 && rw <= max_rw && rw <= ((int64_t)1 << (32 - wbits)), "HIPEIG_TCOOW_RW out of range");
+  // rw < 2^(32 - wbits): 0xFFFFFFFF stays the padding mark (never binding here: rw <= 20224 < 2^15 <= 2^(32 - wbits))
+  HIPEIG_REQUIRE(rw >= 64 && rw <= max_rw && rw < ((int64_t)1 << (32 - wbits)), "HIPEIG_TCOOW_RW out of range");
   BlockedLayout G{};
   G.nunits = (int)((A->nrows + rw - 1) / rw); G.nwin = nwin; G.wbits = wbits; G.rw = (int)rw;
   G.binbits = binbits; G.csplit = csplit;
