@@ -34,6 +34,9 @@ struct GatherLayout {
   __host__ __device__ int64_t slot(int rank) const { return cbase[nchunks - 1] + (int64_t)rank * cstride(nchunks - 1) + h; }
   __host__ __device__ int64_t total() const { return cbase[nchunks]; }
 };
+// Rows per rank of a row-partitioned operator, passed to kernels by value: with the layout it tells which positions of
+// the gathered buffer hold an operand entry (local row i of rank r at pos(r, i), i < n[r]) and which do not.
+struct RankRows { int32_t n[HIPEIG_MAX_RANKS]; };
 
 // ---- the scalar area: ctx->d_scalars and its pinned mirror ctx->h_scalars, HIPEIG_SCALARS doubles each --------------
 // Every offset any translation unit uses, with its length in doubles.  [0, SC_GATHER_OFFS) of the device side holds the
@@ -281,6 +284,7 @@ struct hipeig_csr {
   int32_t last_block_variant, last_block_k;
   int64_t gather_len;        // length of the gathered operand (ncols, or gl.total())
   GatherLayout gl;           // layout of the gathered operand when the columns were remapped (col_stride > 0)
+  RankRows rank_rows;        // rows of every rank when the operator was created (col_stride > 0)
   int variant;               // 0 = auto, 1 = CSR-vector, 2 = CSR-stream, 3 = TCOO (wave units), 4 = TCOO-W, 5 = TCOO-W with fixed-point accumulators
   int last_variant;          // variant used by the most recent launch (0 = none yet)
   int last_launches;         // kernel launches (sweeps) one product with that variant takes

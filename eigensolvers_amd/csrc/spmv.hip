@@ -112,12 +112,38 @@ rowabs_max_kernel(const int32_t* __restrict__ rowptr, const double* __restrict__
   if (threadIdx.x == 0) partials[blockIdx.x] = m;
 }
 
+// The same over the gathered operand of a row-partitioned operator: only positions that hold an operand entry count.
+// The scalar slots behind the last chunk do not (MINRES leaves its share of <y,y> there before every exchange), nor do
+// the tails of a (rank, chunk) piece beyond the rank's rows: no exchange of this operator writes them, and the buffer is
+// the context's, so an earlier operator's operand may still lie there.  A maximum is exact: the same bits on every rank.
+__global__ void __launch_bounds__(HIPEIG_BLOCK) absmax_gathered_kernel(const double* __restrict__ x, GatherLayout gl, RankRows rows,
+                                                                       double* __restrict__ partials) {
+  __shared__ double lds[16];
+  double m = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = gl.total();
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
+    int k = 0;
+    while (k + 1 < gl.nchunks && p >= gl.cbase[k + 1]) ++k;
+    const int64_t q = p - gl.cbase[k], cs = gl.cstride(k);
+    const int r = (int)(q / cs);
+    const int64_t i = q - (int64_t)r * cs;                // offset inside the piece of (rank r, chunk k)
+    if (i >= gl.h || (int64_t)k * gl.h + i >= rows.n[r]) continue;
+    const double v = fabs(x[p]);
+    m = (v > m || v != v) ? v : m;                     // NaN sticks
+  }
+  m = block_max_all(m, lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = m;
+}
+
 // Operand maximum for the fixed-point sweep: per-workgroup maxima into the context's fx area.
 #define HIPEIG_FX_AREA (4 * HIPEIG_WIDE_PARTIALS)      // behind the three partial-sum areas of the MINRES kernels
 int hipeig_fixed_prepare(hipeig_ctx* c, const hipeig_csr* A, const double* xg, TcooView* t) {
   const int g = grid_for(A->gather_len, 8);
   double* area = c->d_partials + HIPEIG_FX_AREA;
-  hipLaunchKernelGGL(absmax_kernel, dim3(g), dim3(HIPEIG_BLOCK), 0, c->stream, xg, A->gather_len, area);
+  if (A->col_stride > 0)
+    hipLaunchKernelGGL(absmax_gathered_kernel, dim3(g), dim3(HIPEIG_BLOCK), 0, c->stream, xg, A->gl, A->rank_rows, area);
+  else
+    hipLaunchKernelGGL(absmax_kernel, dim3(g), dim3(HIPEIG_BLOCK), 0, c->stream, xg, A->gather_len, area);
   t->fx_xmax = area; t->fx_count = g; t->fx_bound = A->absrow_max;
   return 0;
 }
@@ -864,6 +890,7 @@ int hipeig_csr_finalize(hipeig_ctx* c, hipeig_csr* A, const int32_t* rowptr32) {
     HIPEIG_REQUIRE(offs[c->nranks] == A->ncols, "row counts over ranks must add up to ncols");
     HIPEIG_REQUIRE(offs[c->rank] == A->row_offset, "row_offset does not match the rank order");
     HIPEIG_REQUIRE(A->gl.total() < (int64_t)1 << 31, "gathered operand too long for int32 columns");
+    for (int k = 0; k < c->nranks; ++k) A->rank_rows.n[k] = (int32_t)c->row_counts[k];     // each below ncols < 2^31
     int64_t* d_offs = (int64_t*)(c->d_scalars + 1024);
     HIPEIG_CHECK(hipMemcpyAsync(d_offs, offs.data(), sizeof(int64_t) * (c->nranks + 1),
                                 hipMemcpyHostToDevice, c->stream));

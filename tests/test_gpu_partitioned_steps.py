@@ -26,7 +26,8 @@ import pytest
 
 import _hiprec as hp
 import _minres_steps as ms
-from eigensolvers_amd.distributed import LoopbackGroup, row_range
+from _partition_cases import on_ranks
+from eigensolvers_amd.distributed import row_range
 from test_gpu_minres_steps import (BLOCK_EXITS, SMALL_WINDOWS, _check_eigenvector_solution, _check_exit, _opts, _record,
                                    block_raw, block_records, check_steps, single_raw)
 
@@ -35,16 +36,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not hp.EXTENDED, reason="longd
 LONG = ms.LONG_STEPS
 
 
-# ---------------------------------------------------------------- running on ranks
-def on_ranks(P, body):
-    """``body(rank, ctx)`` on P loopback ranks; the group is closed before anything is looked at."""
-    grp = LoopbackGroup(P)
-    try:
-        return grp.run(body)
-    finally:
-        grp.close()
-
-
+# ---------------------------------------------------------------- running on ranks (``on_ranks``: _partition_cases.py)
 def rank_operator(hip, A, P, rank, ctx):
     lo, hi = row_range(A.shape[0], P, rank)
     return hip.HipCsrOperator.from_scipy(A, row_begin=lo, row_end=hi, ctx=ctx), (lo, hi)
