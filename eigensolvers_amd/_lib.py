@@ -96,6 +96,7 @@ SIGNATURES = {
     "hipeig_spmv_shift": [_P, _P, _D, _D, _P, _P],
     "hipeig_spmv_shift_pair": [_P, _P, _D, _D, _D, _P, _P, _P, _P],
     "hipeig_csr_pair_info": [_P, _I64P],
+    "hipeig_csr_dense_info": [_P, _I64P],
     "hipeig_spmm": [_P, _P, C.c_int, _PP, _PP],
     "hipeig_spmm_shift": [_P, _P, C.c_int, _D, _D, _PP, _PP],
     "hipeig_spmm_shift_pairs": [_P, _P, C.c_int, _D, _D, _D, _PP, _PP, _PP, _PP],

@@ -8,6 +8,7 @@
 #pragma once
 #include <type_traits>
 #include "spmm_device.h"
+#include "dense_device.h"
 
 // spmm.hip
 int hipeig_block_pick_variant(hipeig_ctx* c, hipeig_csr* A, int K, int for_solve);
@@ -16,6 +17,8 @@ int hipeig_block_allgather(hipeig_ctx* c, hipeig_csr* A, int K, const double* xb
 int hipeig_block_pack(hipeig_ctx* c, int K, int64_t n, int k, const double* const* cols, double* blk);
 int hipeig_block_unpack(hipeig_ctx* c, int K, int64_t n, int k, const double* blk, double* const* cols);
 int hipeig_rowowner_grid(const hipeig_ctx* c, const hipeig_csr* A);
+// dense.hip
+DenseView hipeig_dense_view(const hipeig_csr* A);
 // comm.hip
 double* hipeig_gather_block_slot(hipeig_ctx* c, const GatherLayout& gl, int K);
 int hipeig_block_reserve(hipeig_ctx* c, const GatherLayout& gl, int K);
@@ -24,8 +27,9 @@ int hipeig_block_reserve(hipeig_ctx* c, const GatherLayout& gl, int K);
 #define BLOCK_PART_STRIDE ((size_t)HIPEIG_MAX_PARTIALS * BCOO_KMAX)
 
 struct BlockSweepPlan {
-  int variant;               // 1 row-owner CSR sweep, 2 window-blocked (TCOO-B)
-  BcooView tview;            // the blocked copy (variant 1: passed along, never read)
+  int variant;               // 1 row-owner CSR sweep, 2 window-blocked (TCOO-B), 3 dense block sweep
+  BcooView tview;            // the blocked copy (variants 1 and 3: passed along, never read)
+  DenseView dview;           // the dense copy of variant 3 (the caller's kernel takes it from the plan)
   size_t lds;                // dynamic LDS of a sweep launch
   int threads;               // per workgroup
   int gA, nsweep;            // workgroups per sweep launch, sweep launches
@@ -40,7 +44,12 @@ static inline int block_sweep_plan_build(hipeig_ctx* c, hipeig_csr* A, int for_s
   if (p->variant < 0) return 1;
   const BlockedLayout& L = A->b[layout_slot(K)];
   p->tview = hipeig_bcoo_view(A, L);
-  const SweepGrid sg = (p->variant == 2) ? blocked_grid(L) : SweepGrid{hipeig_rowowner_grid(c, A), 1};
+  p->dview = hipeig_dense_view(A);                             // variant 3: hipeig_block_pick_variant has reserved the copy
+  // dense: a persistent grid over groups of 4 waves x DenseBlockShape<K>::ROWS rows, one launch, no LDS
+  const SweepGrid sg = (p->variant == 2) ? blocked_grid(L)
+                     : (p->variant == 3) ? SweepGrid{hipeig_dense_grid(A, DenseBlockShape<K>::ROWS * (HIPEIG_BLOCK / HIPEIG_WAVE)), 1}
+                                         : SweepGrid{hipeig_rowowner_grid(c, A), 1};
+  if (p->variant == 3) A->dense_grid_blk = sg.wgs;
   p->gA = sg.wgs; p->nsweep = sg.launches;
   p->lds = (p->variant == 2) ? blocked_lds_bytes(L, K) : 0;
   p->threads = (p->variant == 2) ? BCOO_THREADS : HIPEIG_BLOCK;
@@ -70,6 +79,8 @@ static inline void block_sweep_launch(hipeig_ctx* c, const BlockSweepPlan& p, La
       tv.unit_begin = sw * p.gA;
       launch(integral_constant<int, 2>{}, p.gA, p.threads, p.lds, tv, sw * p.gA);
     }
+  } else if (p.variant == 3) {
+    launch(integral_constant<int, 3>{}, p.gA, p.threads, p.lds, p.tview, 0);
   } else {
     launch(integral_constant<int, 1>{}, p.gA, p.threads, p.lds, p.tview, 0);
   }

@@ -277,15 +277,20 @@ struct hipeig_csr {
                              // on the first hipeig_spmv_shift_pair of a large operator
   BlockedLayout b[3];        // block-operand copies ("TCOO-B", spmm_device.h), one per interleave width: K = 4, 8, 16
                              // (b[layout_slot(K)])
+  double* d_dense;           // dense copy (variant 6, block variant 3; dense.hip): nrows x dense_ld row-major, zero padded
+  int64_t dense_ld;          // doubles per row of that copy: ncols rounded up to a 128-byte line
+  int64_t dense_bytes;       // its size, 0 until built (counted in `bytes`)
+  int32_t dense_grid_vec, dense_grid_blk;   // workgroups of the last dense single-vector / block launch
   int32_t last_pair_fused;   // 1 when the most recent pair product ran as one sweep
   int reproducible;          // automatic choice restricted to bitwise reproducible kernels (hipeig_csr_set_reproducible)
   double absrow_max;         // max_i sum_j |a_ij| over the local rows: overflow bound of the fixed-point sweep (variant 5)
-  int32_t block_variant;     // 0 = automatic, 1 = row-owner CSR, 2 = TCOO-B
+  int32_t block_variant;     // 0 = automatic, 1 = row-owner CSR, 2 = TCOO-B, 3 = dense (opt-in)
   int32_t last_block_variant, last_block_k;
   int64_t gather_len;        // length of the gathered operand (ncols, or gl.total())
   GatherLayout gl;           // layout of the gathered operand when the columns were remapped (col_stride > 0)
   RankRows rank_rows;        // rows of every rank when the operator was created (col_stride > 0)
-  int variant;               // 0 = auto, 1 = CSR-vector, 2 = CSR-stream, 3 = TCOO (wave units), 4 = TCOO-W, 5 = TCOO-W with fixed-point accumulators
+  int variant;               // 0 = auto, 1 = CSR-vector, 2 = CSR-stream, 3 = TCOO (wave units), 4 = TCOO-W, 5 = TCOO-W with fixed-point accumulators,
+                             // 6 = dense row sweep (opt-in, never the automatic choice)
   int last_variant;          // variant used by the most recent launch (0 = none yet)
   int last_launches;         // kernel launches (sweeps) one product with that variant takes
   int lanes_per_row;         // sub-wave width used to reduce one row
@@ -302,6 +307,14 @@ static inline int layout_slot(int K) { return K == 4 ? 0 : K == 8 ? 1 : 2; }
 // *out is left as it was.
 int hipeig_build_binned(hipeig_ctx* c, hipeig_csr* A, const BlockedLayout& geom, unsigned policy, BlockedLayout* out);
 void hipeig_free_layout(BlockedLayout* L);
+
+// The dense copy (dense.hip).  hipeig_dense_refusal: 0, or 2 with the error set when the operator (and, unless null, the
+// context) cannot take the layout.  hipeig_dense_reserve: builds the copy on first use (0; 2 refused; 1 failed).
+// hipeig_dense_grid: the persistent grid of a sweep whose workgroups take `rows_per_wg` rows per step.
+int hipeig_dense_refusal(const hipeig_ctx* c, const hipeig_csr* A);
+int hipeig_dense_reserve(hipeig_ctx* c, hipeig_csr* A);
+int hipeig_dense_grid(const hipeig_csr* A, int rows_per_wg);
+void hipeig_dense_free(hipeig_csr* A);
 
 // Synchronise the compute stream and report a direct-exchange wait that gave up (comm_direct.hip): every path that hands
 // a result to the host goes through this, so a timed-out wait is an error of THAT call, not of some later one.

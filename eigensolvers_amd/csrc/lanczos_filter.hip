@@ -69,10 +69,11 @@ struct LfScalarsEpilogue {
   }
 };
 
-// VARIANT 2: window-blocked (TCOO-B) sweep, 1024 threads; VARIANT 1: row-owner CSR sweep, 256 threads.
+// VARIANT 2: window-blocked (TCOO-B) sweep, 1024 threads; VARIANT 1: row-owner CSR sweep, 256 threads; VARIANT 3: dense
+// block sweep over D (dense_device.h), 256 threads.
 template <int VARIANT, int K>
 __global__ void __launch_bounds__(VARIANT == 2 ? BCOO_THREADS : HIPEIG_BLOCK)
-lf_sweep_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+lf_sweep_kernel(BcooView T, DenseView D, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                 const double* __restrict__ val, int64_t nrows, const LfState* __restrict__ S,
                 const double* __restrict__ rk, const double* __restrict__ rkm1, double* __restrict__ w,
                 double* __restrict__ partials) {
@@ -94,7 +95,8 @@ lf_sweep_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t* _
   epi.s = sh_s[j]; epi.c1 = sh_c1[j]; epi.use_r1 = sh_use[j];
   epi.rk = rk; epi.rkm1 = rkm1; epi.w = w;
   double acc = 0.0;
-  if (VARIANT == 2) bcoo_wg_sweep<K>(T, rk, epi, acc, bcoo_lds);
+  if (VARIANT == 3) dense_block_sweep<K>(D, rk, epi, acc);
+  else if (VARIANT == 2) bcoo_wg_sweep<K>(T, rk, epi, acc, bcoo_lds);
   else csr_rowowner_block_sweep<K>(rowptr, col, val, nrows, rk, epi, acc);
   const double tot = block_reduce_cols<K>(acc, red);
   if (threadIdx.x < K) partials[(size_t)blockIdx.x * K + threadIdx.x] = tot;
@@ -252,7 +254,7 @@ struct LfCombineEpilogue {
 // epilogue then holds NC coefficients per thread and makes NC read-modify-writes of Q per element, nothing else changes.
 template <int VARIANT, int K, int NC>
 __global__ void __launch_bounds__(VARIANT == 2 ? BCOO_THREADS : HIPEIG_BLOCK)
-lf_combine_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+lf_combine_kernel(BcooView T, DenseView D, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                   const double* __restrict__ val, int64_t nrows, const double* __restrict__ tab, const int* __restrict__ m,
                   int step, const double* __restrict__ rk, double* __restrict__ rkm1, double* __restrict__ Q, int64_t nb) {
   __shared__ double sh_tab[LF_TAB(K, NC)];
@@ -269,7 +271,8 @@ lf_combine_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t*
   epi.acc_on = step < sh_m[j]; epi.upd_on = step + 1 < sh_m[j];
   epi.rk = rk; epi.rkm1 = rkm1; epi.Q = Q; epi.nb = nb;
   double acc = 0.0;
-  if (VARIANT == 2) bcoo_wg_sweep<K>(T, rk, epi, acc, bcoo_lds);
+  if (VARIANT == 3) dense_block_sweep<K>(D, rk, epi, acc);
+  else if (VARIANT == 2) bcoo_wg_sweep<K>(T, rk, epi, acc, bcoo_lds);
   else csr_rowowner_block_sweep<K>(rowptr, col, val, nrows, rk, epi, acc);
 }
 
@@ -522,7 +525,7 @@ static int lf_scalars_impl(hipeig_ctx* c, hipeig_csr* A, double sign, int k, con
 
   auto enqueue_sweep = [&](const double* rk, const double* rkm1, double* w) {
     block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int off) {
-      hipLaunchKernelGGL((lf_sweep_kernel<decltype(v)::value, K>), dim3(grid), dim3(threads), lds, c->stream, tv, A->d_rowptr,
+      hipLaunchKernelGGL((lf_sweep_kernel<decltype(v)::value, K>), dim3(grid), dim3(threads), lds, c->stream, tv, plan.dview, A->d_rowptr,
                          A->d_col, A->d_val, n, (const LfState*)V, rk, rkm1, w, pA + (size_t)off * K);
     });
   };
@@ -669,7 +672,7 @@ static int lf_enqueue_products(hipeig_ctx* c, hipeig_csr* A, const double* d_tab
     const double* rk = Vb[i & 1];
     double* rkm1 = Vb[(i + 1) & 1];
     block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int) {      // no partials
-      hipLaunchKernelGGL((lf_combine_kernel<decltype(v)::value, K, NC>), dim3(grid), dim3(threads), lds, c->stream, tv,
+      hipLaunchKernelGGL((lf_combine_kernel<decltype(v)::value, K, NC>), dim3(grid), dim3(threads), lds, c->stream, tv, plan.dview,
                          A->d_rowptr, A->d_col, A->d_val, n, tab, d_m, i, rk, rkm1, Q, nb);
     });
   }

@@ -83,10 +83,11 @@ struct MinresKdArgs {
 // VARIANT 1-4: the operator sweep of that layout.  VARIANT 5: the combine step of a split TCOO-W sweep
 // (T.raw_out holds T.part_base slabs of raw sums, see spmv_device.h) - same prologue, same epilogue.
 // FIXED = 1 (VARIANT 4 only): fixed-point accumulators, public kernel variant 5 (spmv_device.h).
+// VARIANT 6: the dense row sweep over D (dense_device.h).
 // `zero_xx`: a row-partitioned run all-reduces (<v,y>, <x,x>) as one record, so a sweep without a riding KD stores 0 there.
 template <int VARIANT, int FIXED, int PRECOND>
 __global__ void __launch_bounds__(VARIANT == 4 ? TCOOW_THREADS : HIPEIG_BLOCK)
-minres_ka_kernel(CsrView A, TcooView T, const double* __restrict__ xg, MinresArgs a, const MinresState* __restrict__ Sin,
+minres_ka_kernel(CsrView A, TcooView T, DenseView D, const double* __restrict__ xg, MinresArgs a, const MinresState* __restrict__ Sin,
                  MinresState* __restrict__ Sout, const double* __restrict__ src,
                  const double* __restrict__ r1, double* __restrict__ y, MinresRed ra, MinresKdArgs kda, int zero_xx) {
   __shared__ double prod[VARIANT == 2 ? SPMV_NNZ_PER_BLOCK : 8];
@@ -117,7 +118,8 @@ minres_ka_kernel(CsrView A, TcooView T, const double* __restrict__ xg, MinresArg
   epi.src = src; epi.r1 = r1; epi.y = y;
   double acc = 0.0, acc_xx = 0.0;
   epi.zold = kda.zold; epi.w1 = kda.w1; epi.w2 = kda.w2; epi.w = kda.w; epi.x = kda.x; epi.xx = &acc_xx;
-  if (VARIANT == 5) tcoow_combine_sweep(T.raw_out, T.part_base, T.part_stride, T.nrows, epi, acc);
+  if (VARIANT == 6) dense_row_sweep(D, xg, epi, acc);
+  else if (VARIANT == 5) tcoow_combine_sweep(T.raw_out, T.part_base, T.part_stride, T.nrows, epi, acc);
   else if (VARIANT == 4) tcoo_wg_sweep<MinresRowEpilogue<PRECOND>, FIXED>(T, xg, epi, acc, tcoo_lds, red);
   else if (VARIANT == 3) tcoo_sweep(T, xg, epi, acc, tcoo_lds);
   else if (VARIANT == 2) csr_stream_sweep(A, xg, epi, acc, prod);
@@ -399,7 +401,7 @@ static int minres_solve(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign,
       kd.red = MinresRed{pD + off, pD, nPA, (unsigned)nPA, cntD, tot + 1, nullptr};
       const MinresRed ra{pA + off, pA, nPA, (unsigned)nPA, cntA, tot + 0, nullptr};
       const auto ka_kernel = minv ? minres_ka_kernel<decltype(v)::value, decltype(f)::value, 1> : minres_ka_kernel<decltype(v)::value, decltype(f)::value, 0>;
-      hipLaunchKernelGGL(ka_kernel, dim3(grid), dim3(threads), lds, c->stream, plan.view, tv, xg, al, Sin, V + 1, src, r1, yb, ra, kd, dist ? 1 : 0);
+      hipLaunchKernelGGL(ka_kernel, dim3(grid), dim3(threads), lds, c->stream, plan.view, tv, plan.dview, xg, al, Sin, V + 1, src, r1, yb, ra, kd, dist ? 1 : 0);
     });
     if (plan.variant == 4) hipeig_phase_mark(c, 3);
     return 0;

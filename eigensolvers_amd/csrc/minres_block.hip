@@ -99,9 +99,9 @@ static int minres_block_impl(hipeig_ctx* c, hipeig_csr* A, double sigma, double 
   auto launch_ka = [&](const double* xg, double* r2, double* r1, double* yb, bool late) {
     block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int off) {
       if (late) hipLaunchKernelGGL((minres_block_ka_kernel<decltype(v)::value, K, 1>), dim3(grid), dim3(threads), lds, c->stream,
-                                   tv, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)off * K);
+                                   tv, plan.dview, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)off * K);
       else hipLaunchKernelGGL((minres_block_ka_kernel<decltype(v)::value, K>), dim3(grid), dim3(threads), lds, c->stream,
-                              tv, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)off * K);
+                              tv, plan.dview, A->d_rowptr, A->d_col, A->d_val, n, xg, a, V + 0, V + 8, r2, r1, yb, pA + (size_t)off * K);
     });
   };
   // KD of iteration `it` (buffers of that iteration)

@@ -30,12 +30,13 @@ struct MinresBlockEpilogue {
   }
 };
 
-// VARIANT 2: window-blocked (TCOO-B) sweep, 1024 threads; VARIANT 1: row-owner CSR sweep, 256 threads.
+// VARIANT 2: window-blocked (TCOO-B) sweep, 1024 threads; VARIANT 1: row-owner CSR sweep, 256 threads; VARIANT 3: dense
+// block sweep over D (dense_device.h), 256 threads.
 // LATE_TESTS = 1: the form of a row-partitioned run - the stopping tests of the previous iteration are not evaluated
 // here but in KC's prologue, where its <x,x> arrives with the all-reduce that also carries this sweep's <v,y>.
 template <int VARIANT, int K, int LATE_TESTS = 0>
 __global__ void __launch_bounds__(VARIANT == 2 ? BCOO_THREADS : HIPEIG_BLOCK)
-minres_block_ka_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+minres_block_ka_kernel(BcooView T, DenseView D, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                        const double* __restrict__ val, int64_t nrows, const double* __restrict__ xg, MinresArgs a,
                        const MinresState* __restrict__ Sin, MinresState* __restrict__ Sout,
                        const double* __restrict__ r2l, const double* __restrict__ r1, double* __restrict__ y,
@@ -64,7 +65,8 @@ minres_block_ka_kernel(BcooView T, const int32_t* __restrict__ rowptr, const int
   epi.sigma = a.sigma; epi.sign = a.sign; epi.s = sh_s[j]; epi.c1 = sh_c1[j]; epi.use_r1 = sh_use[j];
   epi.r2l = r2l; epi.r1 = r1; epi.y = y;
   double acc = 0.0;
-  if (VARIANT == 2) bcoo_wg_sweep<K>(T, xg, epi, acc, bcoo_lds);
+  if (VARIANT == 3) dense_block_sweep<K>(D, xg, epi, acc);
+  else if (VARIANT == 2) bcoo_wg_sweep<K>(T, xg, epi, acc, bcoo_lds);
   else csr_rowowner_block_sweep<K>(rowptr, col, val, nrows, xg, epi, acc);
   const double tot = block_reduce_cols<K>(acc, red);
   if (threadIdx.x < K) partials[(size_t)blockIdx.x * K + threadIdx.x] = tot;

@@ -159,7 +159,7 @@ static int minres_block_jacobi_impl(hipeig_ctx* c, hipeig_csr* A, double sigma, 
     double* znext = Z[(it + 1) % 2];
     block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int off) {
       hipLaunchKernelGGL((minres_block_ka_kernel<decltype(v)::value, K>), dim3(grid), dim3(threads), lds, c->stream,
-                         tv, A->d_rowptr, A->d_col, A->d_val, n, zk, a, V + 0, V + 8, zk, r1, yb, pA + (size_t)off * K);
+                         tv, plan.dview, A->d_rowptr, A->d_col, A->d_val, n, zk, a, V + 0, V + 8, zk, r1, yb, pA + (size_t)off * K);
     });
     hipLaunchKernelGGL(pmrb_kc_kernel<K>, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 8, V + 16, r2, minv, yb, znext, pC);
     // KD runs behind KC', which has written Z_{k+1} into the other half of the ring

@@ -68,10 +68,10 @@ struct LanczosRowEpilogue {
 };
 
 // VARIANT 1-4: the operator sweep of that layout; 5: the combine step of a column-split TCOO-W sweep; FIXED: fixed-point
-// accumulators (public variant 5) - the instantiations of minres_ka_kernel.
+// accumulators (public variant 5); 6: the dense row sweep over D - the instantiations of minres_ka_kernel.
 template <int VARIANT, int FIXED = 0>
 __global__ void __launch_bounds__(VARIANT == 4 ? TCOOW_THREADS : HIPEIG_BLOCK)
-ms_sweep_kernel(CsrView A, TcooView T, const double* __restrict__ xg, const MsState* __restrict__ Sin,
+ms_sweep_kernel(CsrView A, TcooView T, DenseView D, const double* __restrict__ xg, const MsState* __restrict__ Sin,
                 const double* __restrict__ rk, const double* __restrict__ rkm1, double* __restrict__ w, MinresRed ra) {
   __shared__ double prod[VARIANT == 2 ? SPMV_NNZ_PER_BLOCK : 8];
   __shared__ double red[16];
@@ -83,7 +83,8 @@ ms_sweep_kernel(CsrView A, TcooView T, const double* __restrict__ xg, const MsSt
   epi.c1 = epi.use_r1 ? Sin->beta / Sin->oldb : 0.0;
   epi.rk = rk; epi.rkm1 = rkm1; epi.w = w;
   double acc = 0.0;
-  if (VARIANT == 5) tcoow_combine_sweep(T.raw_out, T.part_base, T.part_stride, T.nrows, epi, acc);
+  if (VARIANT == 6) dense_row_sweep(D, xg, epi, acc);
+  else if (VARIANT == 5) tcoow_combine_sweep(T.raw_out, T.part_base, T.part_stride, T.nrows, epi, acc);
   else if (VARIANT == 4) tcoo_wg_sweep<LanczosRowEpilogue, FIXED>(T, xg, epi, acc, tcoo_lds, red);
   else if (VARIANT == 3) tcoo_sweep(T, xg, epi, acc, tcoo_lds);
   else if (VARIANT == 2) csr_stream_sweep(A, xg, epi, acc, prod);
@@ -338,7 +339,7 @@ extern "C" int hipeig_minres_shifts(hipeig_ctx* c, hipeig_csr* A, double sign, i
     if (sweep_prepare(c, A, plan, rk, &op)) return 4;         // no communicator: the operand itself
     sweep_launch(c, plan, op, [&](auto v, auto f, int grid, int threads, size_t lds, const TcooView& tv, const double* xg, int off) {
       const MinresRed ra{pA + off, pA, nPA, (unsigned)nPA, cntA, tot + 0, nullptr};
-      hipLaunchKernelGGL((ms_sweep_kernel<decltype(v)::value, decltype(f)::value>), dim3(grid), dim3(threads), lds, c->stream, plan.view, tv, xg, Sin, rk, rkm1, w, ra);
+      hipLaunchKernelGGL((ms_sweep_kernel<decltype(v)::value, decltype(f)::value>), dim3(grid), dim3(threads), lds, c->stream, plan.view, tv, plan.dview, xg, Sin, rk, rkm1, w, ra);
     });
     return 0;
   };

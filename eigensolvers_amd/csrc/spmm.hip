@@ -165,12 +165,14 @@ BcooView hipeig_bcoo_view(const hipeig_csr* A, const BlockedLayout& L) {
 }
 
 // Decide between the window-blocked and the row-owner block kernel for interleave width K and build the
-// former's layout (idempotent).  Returns 2 (TCOO-B) or 1 (row-owner), -1 on failure.  for_solve: the caller is the block
-// MINRES, whose sweeps leave per-workgroup partials - it cannot take a layout that needs more than HIPEIG_MAX_PARTIALS
-// workgroups per product and keeps the row-owner kernel there (N = 1e7: 16 sweeps of 256).
+// former's layout (idempotent).  Returns 2 (TCOO-B) or 1 (row-owner), -1 on failure.  The dense block sweep (3) is taken
+// only when pinned, after reserving the dense copy; an operator or context it does not suit is refused (-1), not replaced.
+// for_solve: the caller is the block MINRES, whose sweeps leave per-workgroup partials - it cannot take a layout that needs
+// more than HIPEIG_MAX_PARTIALS workgroups per product and keeps the row-owner kernel there (N = 1e7: 16 sweeps of 256).
 int hipeig_block_pick_variant(hipeig_ctx* c, hipeig_csr* A, int K, int for_solve) {
   BlockedLayout& L = A->b[layout_slot(K)];
   A->last_block_k = K;
+  if (A->block_variant == 3) return hipeig_dense_reserve(c, A) ? -1 : (A->last_block_variant = 3);
   if (A->block_variant == 1 || A->nnz == 0 || A->nrows == 0) return A->last_block_variant = 1;
   // an operator pinned to a reproducible kernel (variants 1-3, 5) keeps that promise for block products and block
   // solves too: the row-owner kernel adds a row's terms in a fixed order, the window-blocked one uses fp64 atomics
@@ -310,6 +312,13 @@ spmm_bcoo_kernel(BcooView T, const double* __restrict__ X, Epi epi) {
 
 template <int K, class Epi>
 __global__ void __launch_bounds__(HIPEIG_BLOCK)
+spmm_dense_kernel(DenseView D, const double* __restrict__ X, Epi epi) {
+  double acc = 0.0;
+  dense_block_sweep<K>(D, X, epi, acc);
+}
+
+template <int K, class Epi>
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
 spmm_rowowner_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const double* __restrict__ val,
                      int64_t nrows, const double* __restrict__ X, Epi epi) {
   double acc = 0.0;
@@ -335,6 +344,8 @@ static int spmm_block_run(hipeig_ctx* c, hipeig_csr* A, const double* Xb, const 
   block_sweep_launch(c, plan, [&](auto v, int grid, int threads, size_t lds, const BcooView& tv, int) {
     if constexpr (decltype(v)::value == 2)
       hipLaunchKernelGGL((spmm_bcoo_kernel<K, Epi>), dim3(grid), dim3(threads), lds, c->stream, tv, xg, epi);
+    else if constexpr (decltype(v)::value == 3)
+      hipLaunchKernelGGL((spmm_dense_kernel<K, Epi>), dim3(grid), dim3(threads), lds, c->stream, plan.dview, xg, epi);
     else
       hipLaunchKernelGGL((spmm_rowowner_kernel<K, Epi>), dim3(grid), dim3(threads), lds, c->stream,
                          A->d_rowptr, A->d_col, A->d_val, A->nrows, xg, epi);
@@ -556,7 +567,8 @@ extern "C" int hipeig_csr_block_info(hipeig_csr* A, int64_t info[4]) {
 }
 
 extern "C" int hipeig_csr_set_block_variant(hipeig_csr* A, int variant) {
-  HIPEIG_REQUIRE(variant >= 0 && variant <= 2, "unknown block variant (0 auto, 1 row-owner, 2 window-blocked)");
+  HIPEIG_REQUIRE(variant >= 0 && variant <= 3, "unknown block variant (0 auto, 1 row-owner, 2 window-blocked, 3 dense)");
+  if (variant == 3 && hipeig_dense_refusal(nullptr, A)) return 2;   // what the operator alone shows; the context at first use
   A->block_variant = variant;
   return 0;
 }

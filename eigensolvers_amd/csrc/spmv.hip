@@ -47,6 +47,12 @@ spmv_tcoow_kernel(TcooView T, const double* __restrict__ x, AxpyEpilogue epi) {
   tcoo_wg_sweep<AxpyEpilogue, FIXED>(T, x, epi, acc, tcoo_lds, red16);
 }
 
+__global__ void __launch_bounds__(HIPEIG_BLOCK)
+spmv_dense_kernel(DenseView D, const double* __restrict__ x, AxpyEpilogue epi) {
+  double acc = 0.0;
+  dense_row_sweep(D, x, epi, acc);
+}
+
 // Complex operand, real operator, complex shift (the contour solves of feast.py:83-90 through GCROT): with
 // x = xr + i xi and z = zr + i zi,  y = sign*(z*x - H x):
 //   yr = sign*(zr*xr - H xr) - sign*zi*xi,   yi = sign*(zr*xi - H xi) + sign*zi*xr.
@@ -156,11 +162,14 @@ spmv_tcoow_combine_kernel(const double* __restrict__ parts, int nparts, int64_t 
 
 // sweep_launch's callback for the product kernels: the one place that names them, for hipeig_spmv, hipeig_spmv_shift and the
 // raw launches of a TCOO-W plan.  They keep a name per layout (bench.py and the committed counter pass look them up by it).
-static auto spmv_launcher(hipeig_ctx* c, const CsrView& view, const AxpyEpilogue& epi) {
+static auto spmv_launcher(hipeig_ctx* c, const SweepPlan& p, const AxpyEpilogue& epi) {
+  const CsrView view = p.view;
+  const DenseView dview = p.dview;
   return [=](auto v, auto f, int grid, int threads, size_t lds, const TcooView& tv, const double* xg, int) {
     constexpr int V = decltype(v)::value;
     const dim3 g(grid), t(threads);
-    if constexpr (V == 5) hipLaunchKernelGGL(spmv_tcoow_combine_kernel, g, t, lds, c->stream, tv.raw_out, tv.part_base, tv.part_stride, tv.nrows, epi);
+    if constexpr (V == 6) hipLaunchKernelGGL(spmv_dense_kernel, g, t, lds, c->stream, dview, xg, epi);
+    else if constexpr (V == 5) hipLaunchKernelGGL(spmv_tcoow_combine_kernel, g, t, lds, c->stream, tv.raw_out, tv.part_base, tv.part_stride, tv.nrows, epi);
     else if constexpr (V == 4) hipLaunchKernelGGL(spmv_tcoow_kernel<decltype(f)::value>, g, t, lds, c->stream, tv, xg, epi);
     else if constexpr (V == 3) hipLaunchKernelGGL(spmv_tcoo_kernel, g, t, lds, c->stream, tv, xg, epi);
     else if constexpr (V == 2) hipLaunchKernelGGL(spmv_stream_kernel, g, t, lds, c->stream, view, xg, epi);
@@ -199,6 +208,7 @@ CsrView hipeig_csr_view(const hipeig_csr* A) {
 
 // Workgroups per launch and sweep launches of one product with `variant` (4 stands for 5 too)
 SweepGrid hipeig_sweep_grid(const hipeig_csr* A, int variant) {
+  if (variant == 6) return SweepGrid{hipeig_dense_grid(A, DENSE_ROWS_PER_WAVE * (HIPEIG_BLOCK / HIPEIG_WAVE)), 1};
   if (variant == 4 || variant == 5) return blocked_grid(A->w);
   if (variant == 3) return blocked_grid(A->t, 4);
   int64_t g = A->n_row_blocks;
@@ -368,7 +378,7 @@ int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const SweepPlan& p, cons
     HIPEIG_REQUIRE(!P.overlapped && P.nlaunch == 1, "the fixed-point sweep takes the plain exchange");
     if (hipeig_fixed_prepare(c, A, o->xg, &P.tv[0])) return 4;
   }
-  const auto raw = spmv_launcher(c, p.view, AxpyEpilogue{0.0, 0.0, nullptr, nullptr});
+  const auto raw = spmv_launcher(c, p, AxpyEpilogue{0.0, 0.0, nullptr, nullptr});
   bool marked = false;
   for (int i = 0; i < P.nlaunch; ++i) {
     if (P.wait[i] >= 0) {
@@ -398,7 +408,7 @@ static int launch_spmv(hipeig_ctx* c, hipeig_csr* A, double a_self, double a_sum
   // shift term: x restricted to this operator's rows.  Partitioned run: x IS that slice; a row
   // slab applied to a full-length operand (single process): the slice starts at row_offset.
   const AxpyEpilogue epi{a_self, a_sum, c->collectives ? x : x + A->row_offset, y};
-  sweep_launch(c, plan, op, spmv_launcher(c, plan.view, epi));
+  sweep_launch(c, plan, op, spmv_launcher(c, plan, epi));
   HIPEIG_CHECK(hipGetLastError());
   hipeig_phase_mark(c, 3);
   return 0;
@@ -822,6 +832,7 @@ int hipeig_csr_build_tcoow(hipeig_ctx* c, hipeig_csr* A) { return build_tcoow_la
 // The variant a launch will use (building the TCOO copy on demand); -1 on failure.
 int hipeig_csr_pick_variant(hipeig_ctx* c, hipeig_csr* A) {
   int variant = A->variant;
+  if (variant == 6 && hipeig_dense_reserve(c, A)) return -1;    // opt-in only; refused, never replaced by another layout
   if (variant == 0) {
     // the gathered operand does not fit one XCD's L2 -> window it; small problems stream
     variant = (A->gather_len * 8 > (int64_t)3 << 20 && A->nnz > (int64_t)1 << 20) ? (A->reproducible ? 5 : 4) : 2;
@@ -957,6 +968,7 @@ extern "C" int hipeig_csr_destroy(hipeig_ctx* c, hipeig_csr* A) {
   if (A->d_val) hipFree(A->d_val);
   if (A->d_row_blocks) hipFree(A->d_row_blocks);
   for (BlockedLayout* L : {&A->t, &A->w, &A->p, &A->b[0], &A->b[1], &A->b[2]}) hipeig_free_layout(L);
+  hipeig_dense_free(A);
   free(A);
   return 0;
 }
@@ -1000,7 +1012,8 @@ extern "C" int hipeig_csr_fixed_info(hipeig_ctx* c, hipeig_csr* A, double out[2]
 }
 
 extern "C" int hipeig_csr_set_variant(hipeig_csr* A, int variant) {
-  HIPEIG_REQUIRE(variant >= 0 && variant <= 5, "unknown variant");
+  HIPEIG_REQUIRE(variant >= 0 && variant <= 6, "unknown variant");
+  if (variant == 6 && hipeig_dense_refusal(nullptr, A)) return 2;   // what the operator alone shows; the context at first use
   A->variant = variant;
   return 0;
 }

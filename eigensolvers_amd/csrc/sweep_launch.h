@@ -12,6 +12,7 @@
 #pragma once
 #include <type_traits>
 #include "spmv_device.h"
+#include "dense_device.h"
 
 CsrView hipeig_csr_view(const hipeig_csr* A);
 TcooView hipeig_tcoo_view(const hipeig_csr* A, const BlockedLayout& L);
@@ -19,14 +20,16 @@ int hipeig_tcoow_reserve(hipeig_ctx* c, const hipeig_csr* A);
 SweepGrid hipeig_sweep_grid(const hipeig_csr* A, int variant);
 int hipeig_csr_pick_variant(hipeig_ctx* c, hipeig_csr* A);
 size_t hipeig_tcoo_lds_bytes(const hipeig_csr* A);
+DenseView hipeig_dense_view(const hipeig_csr* A);
 void hipeig_phase_mark(hipeig_ctx* c, int k);
 const double* hipeig_gathered(hipeig_ctx* c);
 
 struct SweepPlan {
-  int variant;               // 1-4 (the public variant 5 is 4 with `fixed`)
+  int variant;               // 1-4 (the public variant 5 is 4 with `fixed`), 6 the dense row sweep
   int fixed;                 // TCOO-W with fixed-point accumulators: same structure as 4
   CsrView view;
   TcooView tview;            // the blocked copy of variants 3 / 4
+  DenseView dview;           // the dense copy of variant 6 (the caller's kernel takes it from the plan)
   size_t lds;                // dynamic LDS of a sweep launch
   int gA, nsweep;            // workgroups per sweep launch, sweep launches
   bool split;                // column-split TCOO-W: raw slabs + a combine launch that carries the epilogue
@@ -42,16 +45,18 @@ static inline int sweep_plan_build(hipeig_ctx* c, hipeig_csr* A, int combine_gri
   if (p->variant < 0) return 1;
   p->fixed = (p->variant == 5) ? 1 : 0;
   if (p->fixed) p->variant = 4;
-  HIPEIG_REQUIRE(p->variant >= 1 && p->variant <= 4, "unknown sweep layout");
+  HIPEIG_REQUIRE((p->variant >= 1 && p->variant <= 4) || p->variant == 6, "unknown sweep layout");
   if (p->variant == 4 && hipeig_tcoow_reserve(c, A)) return 1;
   p->view = hipeig_csr_view(A);
   p->tview = hipeig_tcoo_view(A, (p->variant == 4) ? A->w : A->t);
+  p->dview = hipeig_dense_view(A);                             // variant 6: hipeig_csr_pick_variant has reserved the copy
   p->lds = (p->variant == 4) ? blocked_lds_bytes(A->w, 1) : (p->variant == 3) ? hipeig_tcoo_lds_bytes(A) : 0;
   const SweepGrid sg = hipeig_sweep_grid(A, p->variant);
   p->gA = sg.wgs; p->nsweep = sg.launches;
   p->split = (p->variant == 4) && A->w.csplit > 1;
   p->gC = combine_grid;
   p->nPA = p->split ? p->gC : p->gA * p->nsweep;
+  if (p->variant == 6) A->dense_grid_vec = p->gA;              // lds = 0, one launch, no split: a persistent grid
   return 0;
 }
 
@@ -81,13 +86,15 @@ int hipeig_tcoow_run_plan(hipeig_ctx* c, hipeig_csr* A, const SweepPlan& p, cons
 static inline int sweep_prepare(hipeig_ctx* c, hipeig_csr* A, const SweepPlan& p, const double* x_local, SweepOperand* o) {
   o->xg = nullptr; o->tv = p.tview; o->has_last = true; o->ncombine = 0;
   if (p.variant == 4) return hipeig_tcoow_run_plan(c, A, p, x_local, o) ? 4 : 0;
+  if (p.variant == 6) { o->xg = x_local; return 0; }           // whole operator, no communicator: no exchange
   return hipeig_allgather_x(c, A->gl, x_local, A->nrows, &o->xg) ? 4 : 0;
 }
 
 // The epilogue launches of one sweep.  `launch(variant, fixed, grid, threads, lds_bytes, tview, xg, partial_offset)` is
 // called once per kernel launch with the first two as std::integral_constant, so that the caller's generic lambda names
 // its kernel as kernel<decltype(variant)::value, decltype(fixed)::value> (variant 5: the combine step, tcoow_combine_sweep on
-// tview.raw_out / part_base / part_stride); workgroup b of that launch owns partial partial_offset + b of the plan's nPA.
+// tview.raw_out / part_base / part_stride; variant 6: dense_row_sweep on the plan's dview); workgroup b of that launch owns
+// partial partial_offset + b of the plan's nPA.
 template <class Launch>
 static inline void sweep_launch(hipeig_ctx* c, const SweepPlan& p, const SweepOperand& o, Launch&& launch) {
   using std::integral_constant;
@@ -110,6 +117,8 @@ static inline void sweep_launch(hipeig_ctx* c, const SweepPlan& p, const SweepOp
       tv.unit_begin = sw * p.gA * 4;
       launch(integral_constant<int, 3>{}, integral_constant<int, 0>{}, p.gA, HIPEIG_BLOCK, p.lds, tv, o.xg, sw * p.gA);
     }
+  } else if (p.variant == 6) {
+    launch(integral_constant<int, 6>{}, integral_constant<int, 0>{}, p.gA, HIPEIG_BLOCK, (size_t)0, tv, o.xg, 0);
   } else if (p.variant == 1) {
     launch(integral_constant<int, 1>{}, integral_constant<int, 0>{}, p.gA, HIPEIG_BLOCK, (size_t)0, tv, o.xg, 0);
   } else {

@@ -336,13 +336,21 @@ class HipCsrOperator:
         return cls.from_csr_arrays(sl.indptr, sl.indices, sl.data, A.shape[1], row_begin, ctx)
 
     @classmethod
-    def from_dense(cls, M, ctx=None):
-        """Dense ndarray stored as a full CSR (every entry kept) - plumbing-size problems."""
+    def from_dense(cls, M, ctx=None, layout=None):
+        """Dense ndarray stored as a full CSR (every entry kept) - plumbing-size problems.  ``layout="dense"`` also pins
+        the operator to the dense row sweeps (``set_variant(6)``, ``set_block_variant(3)``): a row-major fp64 copy, built
+        on the device at the first product, 8 bytes per entry and no gathers.  ``layout=None`` keeps the automatic choice."""
+        if layout not in (None, "dense"):
+            raise ValueError(f'layout must be None or "dense", got {layout!r}')
         M = np.asarray(M, dtype=np.float64)
         n, m = M.shape
         rowptr = np.arange(0, n * m + 1, m, dtype=np.int64)
         col = np.tile(np.arange(m, dtype=np.int32), n)
-        return cls.from_csr_arrays(rowptr, col, M.ravel(), m, 0, ctx)
+        H = cls.from_csr_arrays(rowptr, col, M.ravel(), m, 0, ctx)
+        if layout == "dense":
+            H.set_variant(6)
+            H.set_block_variant(3)
+        return H
 
     @classmethod
     def generate(cls, N, nnz_row=64, seed=7, row_begin=0, row_end=None, ctx=None, **kw):
@@ -422,7 +430,7 @@ class HipCsrOperator:
         return cache[key]
 
     VARIANTS = {0: "none", 1: "csr-vector", 2: "csr-stream", 3: "column-window-blocked(wave)",
-                4: "column-window-blocked(workgroup)", 5: "column-window-blocked(workgroup, fixed-point)"}
+                4: "column-window-blocked(workgroup)", 5: "column-window-blocked(workgroup, fixed-point)", 6: "dense"}
 
     def set_variant(self, variant):
         """Operator kernel: 0 automatic; 1 CSR-vector, 2 CSR-stream, 3 column-window blocked with wave-owned rows
@@ -430,7 +438,11 @@ class HipCsrOperator:
         workgroup-owned rows and fp64 LDS atomics (the fast default for large operators; a row's sum is
         reproducible to rounding only); 5 the same sweep with FIXED-POINT accumulators - integer adds commute, so
         it is bitwise reproducible at the speed of 4, with an absolute error per row of
-        ~nnz_row * 2^-61 * max_i sum_j|a_ij| * max|x| instead of fp64's relative one."""
+        ~nnz_row * 2^-61 * max_i sum_j|a_ij| * max|x| instead of fp64's relative one; 6 the dense row sweep on a
+        row-major fp64 copy built at the first product (``dense_info``): no column indices, no gathers, a row's adds in
+        an order that depends on the number of columns only (bitwise reproducible).  Opt-in: the automatic choice never
+        takes it.  It needs a whole square operator on a context without a communicator and a copy that fits the free
+        device memory; anything else is refused with a message, here or at the first product, never replaced."""
         _lib.call("hipeig_csr_set_variant", self.handle, int(variant))
         self._variant = int(variant)
 
@@ -438,7 +450,8 @@ class HipCsrOperator:
         """``options["reduction"]`` of the vectors: "deterministic" restricts the operator to
         bitwise reproducible kernels - on the automatic choice CSR-stream stays, the fixed-point variant 5 takes the
         place of the fp64-atomic variant 4 (same speed) and block products take the row-owner kernel; an operator
-        pinned to 4 moves to 5.  "fast" undoes both.  An explicitly pinned variant 1-3 is left alone."""
+        pinned to 4 moves to 5.  "fast" undoes both.  An explicitly pinned variant 1-3 or 6 (fixed-order kernels) is left
+        alone."""
         want = (options or {}).get("reduction")
         if want not in (None, "deterministic", "fast"):
             raise ValueError(f'options["reduction"] must be "deterministic" or "fast", got {want!r}')
@@ -486,10 +499,11 @@ class HipCsrOperator:
         _lib.call("hipeig_csr_info", self.handle, info)
         return self.VARIANTS[int(info[4])]
 
-    BLOCK_VARIANTS = {0: "none", 1: "row-owner", 2: "column-window-blocked"}
+    BLOCK_VARIANTS = {0: "none", 1: "row-owner", 2: "column-window-blocked", 3: "dense"}
 
     def set_block_variant(self, variant):
-        """Kernel of the block product / block solve: 0 automatic, 1 row-owner CSR, 2 window-blocked."""
+        """Kernel of the block product / block solve: 0 automatic, 1 row-owner CSR, 2 window-blocked, 3 the dense block
+        sweep on the copy of variant 6 (opt-in, refused under the same conditions)."""
         _lib.call("hipeig_csr_set_block_variant", self.handle, int(variant))
 
     def block_info(self):
@@ -497,6 +511,22 @@ class HipCsrOperator:
         _lib.call("hipeig_csr_block_info", self.handle, info)
         return {"variant": self.BLOCK_VARIANTS[int(info[0])], "row_blocks": int(info[1]), "windows": int(info[2]),
                 "rows_per_block": int(info[3])}
+
+    def dense_info(self):
+        """The dense copy of variant 6 / block variant 3: rows, columns, ``ld`` (doubles per row: the columns rounded up to
+        a 128-byte line), ``bytes`` of the copy (0 until the first dense product built it), rows a wave carries per pass and
+        the workgroups of the last dense single-vector / block launch.  Refreshes ``device_bytes``."""
+        out = (C.c_int64 * 8)()
+        _lib.call("hipeig_csr_dense_info", self.handle, out)
+        info = (C.c_int64 * 8)()
+        _lib.call("hipeig_csr_info", self.handle, info)
+        self.device_bytes = info[5]
+        keys = ("rows", "cols", "ld", "bytes", "rows_per_wave", "workgroups", "block_workgroups")
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
+    def dense_algorithmic_bytes(self):
+        """Bytes one dense product has to move: the matrix once, x once, y once."""
+        return 8 * self.nrows * self.ncols + 8 * self.ncols + 8 * self.nrows
 
     def layout_info(self):
         """Layout constants of the blocked copy the last product ran on (a counter profile is valid for these only)."""

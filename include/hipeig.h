@@ -228,8 +228,16 @@ int hipeig_csr_download(hipeig_ctx* ctx, hipeig_csr* A, int64_t* rowptr, int32_t
                         double* val);
 /* force a kernel variant (0 = automatic choice, 1..4 as above, 5 = variant 4 with fixed-point (int64) LDS
  * accumulators: bitwise reproducible whatever the order in which waves reach a row, same speed; absolute error per
- * row ~ nnz_row * 2^-61 * max_i sum_j|a_ij| * max|x|) */
+ * row ~ nnz_row * 2^-61 * max_i sum_j|a_ij| * max|x|; 6 = dense row sweep on a row-major fp64 copy built on first
+ * use - opt-in only, never the automatic choice; refused, not replaced, on an operator that is not whole and square, on a
+ * context with a communicator and where the copy does not fit the free device memory) */
 int hipeig_csr_set_variant(hipeig_csr* A, int variant);
+/* The dense H of the reference's own drivers and unit tests (numpyVector.py:100 `self.array = H @ self.array`, :152
+ * `sigma*x - H@x` with H an ndarray): out[0] = rows, [1] = columns, [2] = doubles per row of the dense copy (columns
+ * rounded up to a 128-byte line), [3] = bytes of the copy (0 until variant 6 / block variant 3 built it), [4] = rows a
+ * wave carries per pass of the single-vector sweep, [5] / [6] = workgroups of the last dense single-vector / block
+ * launch, [7] = 0 (reserved).                                                                                  */
+int hipeig_csr_dense_info(hipeig_csr* A, int64_t out[8]);
 /* options["reduction"] = "deterministic" of the vectors: on != 0 restricts the AUTOMATIC choice
  * (variant 0) to bitwise reproducible kernels - CSR-stream where it would be picked anyway, variant 5 in place of 4,
  * the row-owner kernel for block products.  A pinned variant is not touched.                                      */
@@ -311,7 +319,8 @@ int hipeig_spmm_shift_pairs_zm(hipeig_ctx* ctx, hipeig_csr* A, int npairs, const
 
 /* Kernel choice of the block product / block solve: 0 = automatic, 1 = row-owner CSR (a wavefront per row,
  * 64-byte gathers from wherever the operand block lives), 2 = column-window blocked (operand windows
- * L2-resident, 8 accumulators per row in LDS).  info[0] = variant of the last block launch, [1] = row
+ * L2-resident, 8 accumulators per row in LDS), 3 = dense block sweep on the dense copy of variant 6 (opt-in only,
+ * refused under the same conditions).  info[0] = variant of the last block launch, [1] = row
  * blocks, [2] = column windows, [3] = rows per row block of the window-blocked layout.              */
 int hipeig_csr_set_block_variant(hipeig_csr* A, int variant);
 int hipeig_csr_block_info(hipeig_csr* A, int64_t info[4]);
