@@ -2,7 +2,7 @@
 
 Public surface (mirrors the reference's module-level names for this path):
 
-    from eigensolvers_amd import (AbstractVector, HipVector, HipCsrOperator, HipContext,
+    from eigensolvers_amd import (AbstractVector, HipVector, HipCsrOperator, HipKronSumOperator, HipContext,
                                   inexactLanczosDiagonalization)
 
 ``HipVector`` plugs into ``inexactLanczosDiagonalization`` exactly where the reference's
@@ -11,7 +11,7 @@ of ``include/hipeig.h`` (``libhipeig.so``).  Importing this package does not tou
 GPU; creating a ``HipContext`` / ``HipVector`` does, and fails loudly without one.
 """
 from .abstract_vector import AbstractVector, LINDEP_DEFAULT_VALUE
-from .hip_vector import HipComplexVector, HipContext, HipCsrOperator, HipVector
+from .hip_vector import HipComplexVector, HipContext, HipCsrOperator, HipKronSumOperator, HipVector
 from .checkpoint import latest_checkpoint, load_checkpoint, save_checkpoint
 from .feast import feastDiagonalization
 from .lanczos import inexactLanczosDiagonalization, KrylovSpace, true_residual_norms
@@ -22,7 +22,8 @@ from .shifted_minres import shifted_minres_host, solve_shifts
 from .subspace import (basisTransformation, find_nearest, get_pick_function_close_to_sigma,
                        get_pick_function_maxOvlp)
 
-__all__ = ["AbstractVector", "LINDEP_DEFAULT_VALUE", "HipContext", "HipCsrOperator", "HipVector", "HipComplexVector",
+__all__ = ["AbstractVector", "LINDEP_DEFAULT_VALUE", "HipContext", "HipCsrOperator", "HipKronSumOperator", "HipVector",
+           "HipComplexVector",
            "feastDiagonalization", "latest_checkpoint", "load_checkpoint", "save_checkpoint",
            "inexactLanczosDiagonalization", "KrylovSpace", "true_residual_norms",
            "basisTransformation", "find_nearest", "get_pick_function_close_to_sigma",

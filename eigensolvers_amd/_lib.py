@@ -97,6 +97,10 @@ SIGNATURES = {
     "hipeig_spmv_shift_pair": [_P, _P, _D, _D, _D, _P, _P, _P, _P],
     "hipeig_csr_pair_info": [_P, _I64P],
     "hipeig_csr_dense_info": [_P, _I64P],
+    "hipeig_kron_create": [_P, C.c_int, _I64P, C.POINTER(_DP), _DP, _PP],
+    "hipeig_kron_destroy": [_P, _P],
+    "hipeig_kron_info": [_P, _I64P],
+    "hipeig_kron_diagonal": [_P, _P, _P],
     "hipeig_spmm": [_P, _P, C.c_int, _PP, _PP],
     "hipeig_spmm_shift": [_P, _P, C.c_int, _D, _D, _PP, _PP],
     "hipeig_spmm_shift_pairs": [_P, _P, C.c_int, _D, _D, _D, _PP, _PP, _PP, _PP],

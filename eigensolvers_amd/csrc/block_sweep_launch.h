@@ -40,6 +40,8 @@ struct BlockSweepPlan {
 // sweep leaves per-workgroup partials (hipeig_block_pick_variant), which have to fit their area.
 template <int K>
 static inline int block_sweep_plan_build(hipeig_ctx* c, hipeig_csr* A, int for_solve, BlockSweepPlan* p) {
+  // its CSR arrays are empty: a block sweep over them would be a silent zero product
+  HIPEIG_REQUIRE(!hipeig_kron_raw(A), "block sweeps are not built for the Kronecker-sum operator: apply it vector by vector");
   p->variant = hipeig_block_pick_variant(c, A, K, for_solve);
   if (p->variant < 0) return 1;
   const BlockedLayout& L = A->b[layout_slot(K)];

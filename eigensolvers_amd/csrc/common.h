@@ -290,12 +290,14 @@ struct hipeig_csr {
   GatherLayout gl;           // layout of the gathered operand when the columns were remapped (col_stride > 0)
   RankRows rank_rows;        // rows of every rank when the operator was created (col_stride > 0)
   int variant;               // 0 = auto, 1 = CSR-vector, 2 = CSR-stream, 3 = TCOO (wave units), 4 = TCOO-W, 5 = TCOO-W with fixed-point accumulators,
-                             // 6 = dense row sweep (opt-in, never the automatic choice)
+                             // 6 = dense row sweep (opt-in, never the automatic choice),
+                             // 7 = Kronecker-sum operator (set by hipeig_kron_create only; nnz = 0, the CSR arrays are empty)
   int last_variant;          // variant used by the most recent launch (0 = none yet)
   int last_launches;         // kernel launches (sweeps) one product with that variant takes
   int lanes_per_row;         // sub-wave width used to reduce one row
   int64_t col_stride;        // > 0 when the columns were remapped to the gathered layout `gl` (= gl.h); 0 = global columns
   int64_t bytes;
+  struct KronRecord* kron;   // Kronecker-sum operator (variant 7, kron.hip): factors, V and the raw-sum buffer; null otherwise
 };
 
 static inline int layout_slot(int K) { return K == 4 ? 0 : K == 8 ? 1 : 2; }
@@ -315,6 +317,11 @@ int hipeig_dense_refusal(const hipeig_ctx* c, const hipeig_csr* A);
 int hipeig_dense_reserve(hipeig_ctx* c, hipeig_csr* A);
 int hipeig_dense_grid(const hipeig_csr* A, int rows_per_wg);
 void hipeig_dense_free(hipeig_csr* A);
+
+// The Kronecker-sum operator (kron.hip).  hipeig_kron_product: raw = H x into the operator's raw-sum buffer, one launch per
+// mode on the compute stream (0, or an error code with the error set).  hipeig_kron_raw: that buffer (null: not such an operator).
+int hipeig_kron_product(hipeig_ctx* c, hipeig_csr* A, const double* x);
+double* hipeig_kron_raw(const hipeig_csr* A);
 
 // Synchronise the compute stream and report a direct-exchange wait that gave up (comm_direct.hip): every path that hands
 // a result to the host goes through this, so a timed-out wait is an error of THAT call, not of some later one.

@@ -98,6 +98,7 @@ extern "C" int hipeig_dense_solve_small(hipeig_ctx* c, hipeig_csr* A, double zr,
                                         const double* b_im, double* x_re, double* x_im, int* singular) {
   HIPEIG_REQUIRE(singular != nullptr && b_re != nullptr && x_re != nullptr, "null argument");
   HIPEIG_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
+  HIPEIG_REQUIRE(!hipeig_kron_raw(A), "the exact small solve reads CSR entries, which a Kronecker-sum operator does not store");
   HIPEIG_REQUIRE(!c->collectives && A->nrows == A->ncols && A->col_stride == 0, "the exact small solve needs the whole square operator on one device");
   HIPEIG_REQUIRE(A->nrows >= 1 && A->nrows <= HIPEIG_DENSE_MAX, "the exact small solve is limited to n <= 96 (it exists for the Fortran known-answer comparison)");
   HIPEIG_REQUIRE((zi == 0.0 && b_im == nullptr) || x_im != nullptr, "a complex system needs x_im");

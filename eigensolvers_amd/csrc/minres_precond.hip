@@ -23,6 +23,7 @@ csr_diagonal_kernel(int64_t nrows, int64_t row_offset, const int32_t* __restrict
 
 extern "C" int hipeig_csr_diagonal(hipeig_ctx* c, hipeig_csr* A, double* d) {
   HIPEIG_REQUIRE(d != nullptr, "null output");
+  HIPEIG_REQUIRE(!hipeig_kron_raw(A), "a Kronecker-sum operator stores no CSR entries: its diagonal is hipeig_kron_diagonal's");
   HIPEIG_REQUIRE(A->col_stride == 0, "the diagonal is taken from global column indices (one GPU, or a row slice before the columns are remapped)");
   if (A->nrows == 0) return 0;
   const int64_t g = (A->nrows + HIPEIG_BLOCK - 1) / HIPEIG_BLOCK;

@@ -25,7 +25,7 @@ void hipeig_phase_mark(hipeig_ctx* c, int k);
 const double* hipeig_gathered(hipeig_ctx* c);
 
 struct SweepPlan {
-  int variant;               // 1-4 (the public variant 5 is 4 with `fixed`), 6 the dense row sweep
+  int variant;               // 1-4 (the public variant 5 is 4 with `fixed`), 6 the dense row sweep, 7 the Kronecker-sum operator
   int fixed;                 // TCOO-W with fixed-point accumulators: same structure as 4
   CsrView view;
   TcooView tview;            // the blocked copy of variants 3 / 4
@@ -35,6 +35,7 @@ struct SweepPlan {
   bool split;                // column-split TCOO-W: raw slabs + a combine launch that carries the epilogue
   int gC;                    // grid of that combine launch
   int nPA;                   // workgroups whose epilogue runs in one sweep: the partials a reducing kernel leaves, side by side
+  const double* kron_raw;    // variant 7: the operator's raw sums, which the combine launch carries the epilogue over
 };
 
 // Picks the layout (building the blocked copy on demand) and sizes one sweep of A.  `combine_grid`: the grid of the combine
@@ -45,7 +46,9 @@ static inline int sweep_plan_build(hipeig_ctx* c, hipeig_csr* A, int combine_gri
   if (p->variant < 0) return 1;
   p->fixed = (p->variant == 5) ? 1 : 0;
   if (p->fixed) p->variant = 4;
-  HIPEIG_REQUIRE((p->variant >= 1 && p->variant <= 4) || p->variant == 6, "unknown sweep layout");
+  HIPEIG_REQUIRE((p->variant >= 1 && p->variant <= 4) || p->variant == 6 || p->variant == 7, "unknown sweep layout");
+  p->kron_raw = hipeig_kron_raw(A);
+  HIPEIG_REQUIRE((p->variant == 7) == (p->kron_raw != nullptr), "variant 7 belongs to the operators of hipeig_kron_create, and they take no other");
   if (p->variant == 4 && hipeig_tcoow_reserve(c, A)) return 1;
   p->view = hipeig_csr_view(A);
   p->tview = hipeig_tcoo_view(A, (p->variant == 4) ? A->w : A->t);
@@ -57,6 +60,7 @@ static inline int sweep_plan_build(hipeig_ctx* c, hipeig_csr* A, int combine_gri
   p->gC = combine_grid;
   p->nPA = p->split ? p->gC : p->gA * p->nsweep;
   if (p->variant == 6) A->dense_grid_vec = p->gA;              // lds = 0, one launch, no split: a persistent grid
+  if (p->variant == 7) { p->gA = p->gC; p->nsweep = 1; p->nPA = p->gC; }   // the one epilogue launch is the combine launch: no LDS, no blocked copy
   return 0;
 }
 
@@ -87,13 +91,18 @@ static inline int sweep_prepare(hipeig_ctx* c, hipeig_csr* A, const SweepPlan& p
   o->xg = nullptr; o->tv = p.tview; o->has_last = true; o->ncombine = 0;
   if (p.variant == 4) return hipeig_tcoow_run_plan(c, A, p, x_local, o) ? 4 : 0;
   if (p.variant == 6) { o->xg = x_local; return 0; }           // whole operator, no communicator: no exchange
+  if (p.variant == 7) {                                        // the same, and the product itself: raw sums into the operator's buffer
+    o->xg = x_local;
+    return hipeig_kron_product(c, A, x_local) ? 4 : 0;
+  }
   return hipeig_allgather_x(c, A->gl, x_local, A->nrows, &o->xg) ? 4 : 0;
 }
 
 // The epilogue launches of one sweep.  `launch(variant, fixed, grid, threads, lds_bytes, tview, xg, partial_offset)` is
 // called once per kernel launch with the first two as std::integral_constant, so that the caller's generic lambda names
 // its kernel as kernel<decltype(variant)::value, decltype(fixed)::value> (variant 5: the combine step, tcoow_combine_sweep on
-// tview.raw_out / part_base / part_stride; variant 6: dense_row_sweep on the plan's dview); workgroup b of that launch owns
+// tview.raw_out / part_base / part_stride; variant 6: dense_row_sweep on the plan's dview; a Kronecker-sum operator: that
+// combine step alone, over the one slab sweep_prepare left in the operator's raw buffer); workgroup b of that launch owns
 // partial partial_offset + b of the plan's nPA.
 template <class Launch>
 static inline void sweep_launch(hipeig_ctx* c, const SweepPlan& p, const SweepOperand& o, Launch&& launch) {
@@ -117,6 +126,10 @@ static inline void sweep_launch(hipeig_ctx* c, const SweepPlan& p, const SweepOp
       tv.unit_begin = sw * p.gA * 4;
       launch(integral_constant<int, 3>{}, integral_constant<int, 0>{}, p.gA, HIPEIG_BLOCK, p.lds, tv, o.xg, sw * p.gA);
     }
+  } else if (p.variant == 7) {
+    tv.raw_out = const_cast<double*>(p.kron_raw);
+    tv.part_base = 1; tv.part_stride = 0;                         // one slab of tv.nrows raw sums
+    launch(integral_constant<int, 5>{}, integral_constant<int, 0>{}, p.gC, HIPEIG_BLOCK, (size_t)0, tv, o.xg, 0);
   } else if (p.variant == 6) {
     launch(integral_constant<int, 6>{}, integral_constant<int, 0>{}, p.gA, HIPEIG_BLOCK, (size_t)0, tv, o.xg, 0);
   } else if (p.variant == 1) {

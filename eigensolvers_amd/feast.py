@@ -331,6 +331,9 @@ def feastDiagonalization(A, Y, nc, quad, eMin, eMax, eConv, maxit, contourEllips
     nsub = len(Y)
     shared = _shares_lanczos(cls, Y[0])
     filtered = _filters_lanczos(cls, Y[0])
+    if contourPool or filtered:
+        from .hip_vector import _need_block_sweeps
+        _need_block_sweeps(A, "contourPool=True" if contourPool else "linearSolver='lanczos_filter'")
     if filtered and contourPool:
         raise ValueError("contourPool=True pools GCROT solves; linearSolver='lanczos_filter' forms the filtered vectors of "
                          "all contour points from two Lanczos passes - use one or the other")

@@ -186,3 +186,25 @@ def sinc_dvr_harmonic(N=45, xrange=(-10.0, 10.0)):
         T = np.where(d == 0, np.pi ** 2 / 3.0, 2.0 / (d.astype(float) ** 2))
     T = T * (-1.0) ** np.abs(d) / dx ** 2
     return T + np.diag(x ** 2), x
+
+
+def coupled_oscillator_grid(dims, ranges, freqs, coupled=True):
+    """``(factors, V)`` of a D-dimensional oscillator on the direct-product sinc-DVR grid ``dims``, the factored form
+    ``HipKronSumOperator.from_factors`` takes:  H = sum_d I (x) T_d (x) I + diag(V).
+
+    ``T_d`` is the kinetic matrix of mode d: ``sinc_dvr_harmonic(n_d, ranges[d])`` minus its ``diag(x^2)``.  ``V`` (shape
+    ``dims``) is ``sum_d (w_d x_d)^2 + 0.3 prod_d x_d + 0.2 x_1^2 x_D`` on the grid; the last two terms couple the modes,
+    ``coupled=False`` drops them, and the spectrum is then the set of sums of the eigenvalues of ``T_d + diag((w_d x_d)^2)``."""
+    dims = tuple(int(n) for n in dims)
+    if not (len(dims) == len(ranges) == len(freqs)):
+        raise ValueError(f"{len(dims)} dims, {len(ranges)} ranges and {len(freqs)} frequencies")
+    factors, grids = [], []
+    for n, r in zip(dims, ranges):
+        Hd, x = sinc_dvr_harmonic(n, r)
+        factors.append(Hd - np.diag(x ** 2))
+        grids.append(x)
+    mesh = np.meshgrid(*grids, indexing="ij")
+    V = sum((w * xd) ** 2 for w, xd in zip(freqs, mesh))
+    if coupled:
+        V = V + 0.3 * np.prod(mesh, axis=0) + 0.2 * mesh[0] ** 2 * mesh[-1]
+    return factors, np.ascontiguousarray(V, dtype=np.float64)

@@ -95,6 +95,13 @@ def _gcrot_preconditioner(o, x0=None, ctx=None, H=None):
     return float(floor)
 
 
+def _need_block_sweeps(H, what):
+    """An explicit opt-in that rests on block sweeps, on an operator that has none: ``NotImplementedError`` naming it."""
+    if isinstance(H, HipCsrOperator) and not H.supports_block_sweeps:
+        raise NotImplementedError(f"{what} needs block sweeps, which {type(H).__name__} does not have: its products and "
+                                  "solves run vector by vector")
+
+
 def _ptr_table(bufs):
     arr = (C.c_void_p * len(bufs))(*[b.ptr for b in bufs])
     return C.cast(arr, C.POINTER(C.c_void_p)), arr
@@ -297,6 +304,10 @@ class DeviceBuffer:
 class HipCsrOperator:
     """Device-resident sparse symmetric operator (local rows of a row partition)."""
 
+    # Block sweeps (block products, lock-step solves, the Lanczos filter) exist for this operator: consulted wherever a
+    # lock-step path is chosen, so that an operator without them takes the one-by-one calls.
+    supports_block_sweeps = True
+
     def __init__(self, ctx, handle):
         self.ctx = ctx
         self.handle = handle
@@ -314,6 +325,8 @@ class HipCsrOperator:
 
     @classmethod
     def from_csr_arrays(cls, rowptr, col, val, ncols, row_offset=0, ctx=None):
+        if np.iscomplexobj(val):
+            raise TypeError("HipCsrOperator holds real fp64 operators")
         ctx = ctx or HipContext.default()
         rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
         col = np.ascontiguousarray(col, dtype=np.int32)
@@ -342,6 +355,8 @@ class HipCsrOperator:
         on the device at the first product, 8 bytes per entry and no gathers.  ``layout=None`` keeps the automatic choice."""
         if layout not in (None, "dense"):
             raise ValueError(f'layout must be None or "dense", got {layout!r}')
+        if np.iscomplexobj(M):
+            raise TypeError("HipCsrOperator holds real fp64 operators")
         M = np.asarray(M, dtype=np.float64)
         n, m = M.shape
         rowptr = np.arange(0, n * m + 1, m, dtype=np.int64)
@@ -686,6 +701,199 @@ class HipCsrOperator:
         return NotImplemented
 
 
+class HipKronSumOperator(HipCsrOperator):
+    """Kronecker-sum operator on a direct-product grid, applied factor by factor on the matrix cores::
+
+        H = sum_d  I_(n_1..n_{d-1}) (x) T_d (x) I_(n_{d+1}..n_D)  +  diag(V),      N = n_1 * ... * n_D
+
+    with dense ``n_d x n_d`` factors and a general diagonal ``V`` (where the modes couple): the vibrational Hamiltonians in
+    a product / DVR basis.  The vector index is in C order, last mode fastest: ``r = ((i_1 n_2 + i_2) n_3 + ...) + i_D``.
+    As a ``HipCsrOperator`` it passes every gate of the solvers; what a single vector does with an operator - ``applyOp``,
+    ``matrixRepresentation``, ``solve`` with ``minres`` (plain, Jacobi), ``minres_shifted`` and ``gcrotmk``, the Lanczos
+    and FEAST drivers - is inherited.  Block sweeps are not built (``supports_block_sweeps``):
+    ``solveBlock`` and every automatic lock-step choice solve one by one, ``apply_block`` loops over single products, and
+    the explicit opt-ins that need them raise ``NotImplementedError``.  A row's adds are in an order the dims alone fix:
+    bitwise reproducible."""
+
+    supports_block_sweeps = False
+    VARIANTS = {**HipCsrOperator.VARIANTS, 7: "kronecker-sum"}          # the variant hipeig_kron_create pins; it cannot be set
+    MAX_MODES = 8
+    KERNEL_FORMS = {1: "mfma", 2: "mfma-last", 3: "plain"}
+
+    def __init__(self, ctx, handle, factors, diag):
+        super().__init__(ctx, handle)
+        self._finalizer.detach()
+        self._finalizer = weakref.finalize(self, HipKronSumOperator._destroy, ctx, handle)
+        self._factors = factors
+        self._diag = diag
+        self.dims = tuple(int(t.shape[0]) for t in factors)
+        self._variant = 7
+
+    @staticmethod
+    def _destroy(ctx, handle):
+        _lib.load().hipeig_kron_destroy(ctx.handle, handle)
+
+    @staticmethod
+    def _checked(factors, diag, check):
+        """The host side of ``from_factors``: ``(factors, V or None)`` as contiguous fp64 arrays, or the refusal."""
+        factors = list(factors)
+        if not 1 <= len(factors) <= HipKronSumOperator.MAX_MODES:
+            raise ValueError(f"a Kronecker sum takes 1 to {HipKronSumOperator.MAX_MODES} factors, got {len(factors)}")
+        out = []
+        for d, T in enumerate(factors, 1):
+            if np.iscomplexobj(T):
+                raise TypeError("HipKronSumOperator holds real fp64 factors")
+            T = np.ascontiguousarray(T, dtype=np.float64)
+            if T.ndim != 2 or T.shape[0] != T.shape[1] or T.shape[0] < 1:
+                raise ValueError(f"factor {d} is not a square matrix: shape {T.shape}")
+            if check:
+                if not np.all(np.isfinite(T)):
+                    raise ValueError(f"factor {d} is not finite")
+                if np.max(np.abs(T - T.T)) > 1e-12 * np.max(np.abs(T)):
+                    raise ValueError(f"factor {d} is not symmetric to 1e-12 * max|T| (check=False applies it as given)")
+            out.append(T)
+        dims = tuple(T.shape[0] for T in out)
+        N = int(np.prod([int(n) for n in dims], dtype=object))
+        if N >= 2 ** 31:
+            raise ValueError(f"N = {N} does not stay below 2^31")
+        V = None
+        if diag is not None:
+            if np.iscomplexobj(diag):
+                raise TypeError("HipKronSumOperator holds a real fp64 diagonal")
+            V = np.asarray(diag, dtype=np.float64)
+            if V.shape != dims and V.shape != (N,):
+                raise ValueError(f"diag has shape {V.shape}: expected {dims} or ({N},)")
+            V = np.ascontiguousarray(V.reshape(N))
+            if check and not np.all(np.isfinite(V)):
+                raise ValueError("diag is not finite")
+        return out, V
+
+    @classmethod
+    def from_factors(cls, factors, diag=None, ctx=None, check=True):
+        """``factors``: the ``T_d``, dense and square, ``1 <= D <= 8``, ``n_d >= 1``, ``N < 2^31``; ``diag``: ``None``, an
+        array of shape ``dims`` or of length ``N``.  ``check=True`` raises ``ValueError`` for a factor that is not square,
+        not finite or not symmetric to ``1e-12 * max|T_d|``; ``check=False`` applies the factors as given (``T_d[i, k]``,
+        not transposed).  A factor larger than the kernels take (``kron_info()["max_factor"]``) and a context with a
+        communicator are refused with a message: there is no slow path."""
+        factors, V = cls._checked(factors, diag, check)
+        ctx = ctx or HipContext.default()
+        if ctx.collectives or ctx.direct_only or ctx.nranks > 1:
+            raise ValueError("HipKronSumOperator does not take a context with a communicator (a row partition, its "
+                             "HIPEIG_FORCE_COLLECTIVES rehearsal or a direct-only exchange)")
+        D = len(factors)
+        DP = C.POINTER(C.c_double)
+        dims = (C.c_int64 * D)(*[T.shape[0] for T in factors])
+        tab = (DP * D)(*[T.ctypes.data_as(DP) for T in factors])
+        h = C.c_void_p()
+        try:
+            _lib.call("hipeig_kron_create", ctx.handle, D, dims, tab, None if V is None else V.ctypes.data_as(DP), C.byref(h))
+        except _lib.HipEigError as exc:
+            if "status 2" in str(exc):                    # a refusal with a message, not a failure
+                raise ValueError(str(exc)) from None
+            raise
+        return cls(ctx, h, factors, V)
+
+    # ---- what it is ---------------------------------------------------------------------------------------------
+    def kron_info(self):
+        """Launches per product (one per mode and the one that carries the row epilogue), per mode the kernel form
+        (``"mfma"``: matrix cores, inner stride >= 16; ``"mfma-last"``: matrix cores, last mode; ``"plain"``: FMA chain,
+        inner stride 2..15 or a singleton mode) and the padded size of the device copy of its factor."""
+        out = (C.c_int64 * 40)()
+        _lib.call("hipeig_kron_info", self.handle, out)
+        D = int(out[0])
+        return {"modes": D, "n": int(out[1]), "launches": int(out[2]), "device_bytes": int(out[3]),
+                "raw_bytes": int(out[4]), "max_factor": int(out[5]),
+                "kernels": [self.KERNEL_FORMS[int(out[8 + 4 * d])] for d in range(D)],
+                "padded": [(int(out[10 + 4 * d]), int(out[11 + 4 * d])) for d in range(D)]}
+
+    def algorithmic_bytes(self):
+        """Bytes one product has to move: every mode launch reads x, reads the running sums (the first one V, when there
+        is one) and writes them, 3 streams of 8 N; the epilogue launch reads the sums and writes y, 2 more; the factors
+        once: ``(3 D + 2) * 8 N + 8 sum_d n_d^2``.  An upper bound: on the chip the vector streams of a problem that fits
+        the last-level cache do not all reach HBM."""
+        N, D = self.nrows, len(self.dims)
+        return (3 * D + 2) * 8 * N + 8 * sum(n * n for n in self.dims)
+
+    def diagonal(self):
+        """Device buffer with ``sum_d T_d[i_d, i_d] + V``, summed in the order of ``to_scipy()``; built once."""
+        d = getattr(self, "_diagonal", None)
+        if d is None:
+            d = self.ctx.alloc(self.nrows)
+            _lib.call("hipeig_kron_diagonal", self.ctx.handle, self.handle, d.ptr)
+            self._diagonal = d
+        return d
+
+    @staticmethod
+    def explicit_matrix(factors, diag=None):
+        """The same matrix as host CSR: ``((K_1 + K_2) + ...) + diag(V)`` with ``K_d = I (x) T_d (x) I``
+        (``scipy.sparse.kron``) - for checks and small problems.  Needs no device."""
+        import scipy.sparse as sp
+        dims = [int(np.shape(T)[0]) for T in factors]
+        H = None
+        for d, T in enumerate(factors):
+            o = int(np.prod(dims[:d], dtype=np.int64))
+            s = int(np.prod(dims[d + 1:], dtype=np.int64))
+            K = sp.kron(sp.kron(sp.identity(o, format="csr"), sp.csr_matrix(np.asarray(T, dtype=np.float64)), format="csr"),
+                        sp.identity(s, format="csr"), format="csr")
+            H = K if H is None else H + K
+        if diag is not None:
+            H = H + sp.diags(np.asarray(diag, dtype=np.float64).reshape(-1), format="csr")
+        return sp.csr_matrix(H)
+
+    def to_scipy(self):
+        return self.explicit_matrix(self._factors, self._diag)
+
+    # ---- block forms: loops over single products, or refusals ---------------------------------------------------------
+    def apply_block(self, xs):
+        """``[H x for x in xs]``, one single product after the other."""
+        ys = [self.ctx.alloc(self.nrows) for _ in xs]
+        for x, y in zip(xs, ys):
+            self.apply(x, y)
+        return ys
+
+    def _no_block(self, what):
+        raise NotImplementedError(f"{what} needs block sweeps, which HipKronSumOperator does not have: its products and "
+                                  "solves run vector by vector")
+
+    def apply_shifted_block(self, sigma, xs, reverse=False):
+        self._no_block("apply_shifted_block")
+
+    def apply_shifted_pairs(self, z, xs, reverse=False):
+        self._no_block("apply_shifted_pairs")
+
+    def apply_shifted_block_m(self, sigma, minv, xs, reverse=False):
+        self._no_block("apply_shifted_block_m")
+
+    def apply_shifted_pairs_m(self, zs, minvs, xs, reverse=False):
+        """One operand: the scaling and the single pair product (the preconditioned complex GCROT solve); more need block
+        sweeps."""
+        if len(xs) != 1:
+            self._no_block("apply_shifted_pairs_m on several operands")
+        z = np.asarray(zs, dtype=np.complex128).reshape(-1)[0]
+        t = self.diag_mul(minvs[0], xs[0])
+        y = (self.ctx.alloc(self.nrows), self.ctx.alloc(self.nrows))
+        self.apply_shifted_pair(z, t[0], t[1], y[0], y[1], reverse=reverse)
+        return [y]
+
+    def set_variant(self, variant):
+        self._no_block("set_variant (the CSR layouts)")
+
+    def set_block_variant(self, variant):
+        self._no_block("set_block_variant")
+
+    def set_reproducible(self, on=True):
+        self._no_block("set_reproducible (a choice among the CSR kernels; this product is bitwise reproducible as it is)")
+
+    def set_reduction(self, mode):
+        self._no_block("set_reduction (a choice among the CSR kernels; this product is bitwise reproducible as it is)")
+
+    def honour_reduction_option(self, options):
+        """``options["reduction"]`` is validated and met as it stands: the product has one kernel order, fixed by the dims."""
+        want = (options or {}).get("reduction")
+        if want not in (None, "deterministic", "fast"):
+            raise ValueError(f'options["reduction"] must be "deterministic" or "fast", got {want!r}')
+
+
 class HipVector(AbstractVector):
     """Device-resident fp64 vector with the NumpyVector interface.  A complex array gives a
     ``HipComplexVector`` (two real halves), the counterpart of a complex-dtype NumpyVector."""
@@ -995,6 +1203,7 @@ class HipVector(AbstractVector):
         budget keep the vectors that fit; ``["lanczosBasisPrecision"]: "fp32"`` (only with ``"keep"`` too) stores the basis
         in fp32."""
         from .lanczos_filter import lanczos_filter
+        _need_block_sweeps(H, 'linearSolver="lanczos_filter"')
         B = list(B)
         o = B[0].options if B else {}
         if B:
@@ -1048,6 +1257,7 @@ class HipVector(AbstractVector):
                     and len(bs) >= HipVector.BLOCK_SOLVE_MIN and isinstance(H, HipCsrOperator)
                     and all(isinstance(b, HipVector) for b in bs)
                     and not bs[0].ctx.collectives and not bs[0].ctx.direct_only):
+                _need_block_sweeps(H, '"preconditionerLockStep": True')
                 sols = HipVector._solve_block_minres(H, bs, float(sigma), o, reverseGF, jacobi=True)
                 if onSolution is not None:
                     for i, xs in enumerate(sols):
@@ -1079,8 +1289,8 @@ class HipVector(AbstractVector):
         def whole():
             # whole vectors on a context without collectives (one GPU, or FEAST's contour replicas): the split Arnoldi steps
             # run on one GPU only; a row partition - or one rank rehearsing it with HIPEIG_FORCE_COLLECTIVES - solves one by one
-            return (isinstance(H, HipCsrOperator) and not bs[0].ctx.direct_only and not bs[0].ctx.collectives
-                    and all(isinstance(b, HipVector) for b in bs))
+            return (isinstance(H, HipCsrOperator) and H.supports_block_sweeps and not bs[0].ctx.direct_only
+                    and not bs[0].ctx.collectives and all(isinstance(b, HipVector) for b in bs))
 
         if o["linearSolver"] == "gcrotmk" and complex_shift and x0 is None and len(bs) >= 2 and whole():
             return HipVector._solve_complex_block(H, bs, complex(sigma), o, reverseGF)
@@ -1091,7 +1301,7 @@ class HipVector(AbstractVector):
                 return HipVector._solve_real_block(H, bs, float(sigma), o, reverseGF)
         if (o["linearSolver"] != "minres" or isinstance(sigma, complex) or np.iscomplexobj(sigma)
                 or x0 is not None or len(bs) < HipVector.BLOCK_SOLVE_MIN or not isinstance(H, HipCsrOperator)
-                or bs[0].ctx.direct_only):
+                or not H.supports_block_sweeps or bs[0].ctx.direct_only):
             return [HipVector.solve(H, b, sigma, x0, opType, reverseGF) for b in bs]
         return HipVector._solve_block_minres(H, bs, float(sigma), o, reverseGF)
 
@@ -1265,7 +1475,7 @@ class HipVector(AbstractVector):
         if len(shifts) != len(bs):
             raise ValueError(f"{len(shifts)} shifts for {len(bs)} right-hand sides")
         o = bs[0].options["linearSystemArgs"]
-        if (o["linearSolver"] == "gcrotmk" and x0 is None and isinstance(H, HipCsrOperator)
+        if (o["linearSolver"] == "gcrotmk" and x0 is None and isinstance(H, HipCsrOperator) and H.supports_block_sweeps
                 and all(isinstance(z, (complex, np.complexfloating)) for z in shifts)
                 and all(isinstance(b, HipVector) for b in bs)
                 and not bs[0].ctx.direct_only and not bs[0].ctx.collectives):

@@ -230,7 +230,8 @@ int hipeig_csr_download(hipeig_ctx* ctx, hipeig_csr* A, int64_t* rowptr, int32_t
  * accumulators: bitwise reproducible whatever the order in which waves reach a row, same speed; absolute error per
  * row ~ nnz_row * 2^-61 * max_i sum_j|a_ij| * max|x|; 6 = dense row sweep on a row-major fp64 copy built on first
  * use - opt-in only, never the automatic choice; refused, not replaced, on an operator that is not whole and square, on a
- * context with a communicator and where the copy does not fit the free device memory) */
+ * context with a communicator and where the copy does not fit the free device memory).  7 is the Kronecker-sum operator's
+ * and cannot be set: hipeig_kron_create pins it. */
 int hipeig_csr_set_variant(hipeig_csr* A, int variant);
 /* The dense H of the reference's own drivers and unit tests (numpyVector.py:100 `self.array = H @ self.array`, :152
  * `sigma*x - H@x` with H an ndarray): out[0] = rows, [1] = columns, [2] = doubles per row of the dense copy (columns
@@ -238,6 +239,37 @@ int hipeig_csr_set_variant(hipeig_csr* A, int variant);
  * wave carries per pass of the single-vector sweep, [5] / [6] = workgroups of the last dense single-vector / block
  * launch, [7] = 0 (reserved).                                                                                  */
 int hipeig_csr_dense_info(hipeig_csr* A, int64_t out[8]);
+
+/* ---- Kronecker-sum operator on a direct-product grid ---------------------------------------------------------
+ * H = sum_d I (x) T_d (x) I + diag(V), N = n_1 * ... * n_D, vector index in C order (last mode fastest).  The reference
+ * asks of an operator only H@x, H.shape and H.dtype (numpyVector.py:98-100 applyOp, :147-163 the linear operator of
+ * solve, :180-189 matrixRepresentation), so its users hand over whatever applies fastest; for the vibrational
+ * Hamiltonians in a product / DVR basis the method was written for (examples/stateFollowingHO.py) that is the factored
+ * form.  The handle is an hipeig_csr (kernel variant 7, nnz = 0, an empty CSR behind it) and goes wherever a single
+ * vector meets the operator: hipeig_spmv, hipeig_spmv_shift, hipeig_spmv_shift_pair, hipeig_minres, hipeig_minres_x0,
+ * hipeig_minres_jacobi, hipeig_minres_shifts.  The block entry points (hipeig_spmm*, hipeig_minres_block*,
+ * hipeig_lanczos_block_scalars, hipeig_lanczos_combine), hipeig_csr_diagonal and hipeig_dense_solve_small refuse it.
+ * The adds of a row are in an order fixed by the dims alone (csrc/kron_device.h): bitwise reproducible.
+ *
+ * hipeig_kron_create (numpyVector.py:100 `H @ self.array`, :152/:154 `sigma*x - H@x`): 1 <= D <= 8 modes, dims[d] = n_d
+ * with 1 <= n_d <= 208 and N < 2^31; factors[d] = T_d on the host, n_d x n_d row-major, applied as given (T_d[i][k], not
+ * transposed, symmetric or not); diag = V on the host, N doubles, or NULL.  Refused with a message: a context with a
+ * communicator, a factor the kernels do not take.  Device copies: the factors zero-padded to a multiple of 16 rows and 4
+ * columns, V, and an N-double raw-sum buffer.                                                                      */
+int hipeig_kron_create(hipeig_ctx* ctx, int D, const int64_t* dims, const double* const* factors, const double* diag,
+                       hipeig_csr** out);
+/* frees the Kronecker record and the handle (in place of hipeig_csr_destroy)                                       */
+int hipeig_kron_destroy(hipeig_ctx* ctx, hipeig_csr* A);
+/* What one `H @ x` (numpyVector.py:100) costs: out[0] = modes, [1] = N, [2] = kernel launches per product (one per mode
+ * + the launch that carries the caller's row epilogue over the raw sums), [3] = device bytes, [4] = bytes of the raw-sum
+ * buffer, [5] = largest n_d the kernels take; per mode d (0-based) out[8 + 4 d] = kernel form (1 = matrix cores, inner
+ * stride >= 16; 2 = matrix cores, last mode; 3 = plain FMA: inner stride 2..15 or n_d = 1), [9 + 4 d] = n_d,
+ * [10 + 4 d] / [11 + 4 d] = padded rows / columns of the device copy of T_d.                                       */
+int hipeig_kron_info(hipeig_csr* A, int64_t out[40]);
+/* d[r] = ((T_1[i_1][i_1] + T_2[i_2][i_2]) + ...) + V[r] (device pointer, N doubles): the diagonal of the Jacobi
+ * preconditioner (scipy.sparse.linalg.minres(..., M=), the solve of numpyVector.py:163 with a preconditioner), in
+ * the order in which the explicit matrix sums its terms.                                                          */
+int hipeig_kron_diagonal(hipeig_ctx* ctx, hipeig_csr* A, double* d);
 /* options["reduction"] = "deterministic" of the vectors: on != 0 restricts the AUTOMATIC choice
  * (variant 0) to bitwise reproducible kernels - CSR-stream where it would be picked anyway, variant 5 in place of 4,
  * the row-owner kernel for block products.  A pinned variant is not touched.                                      */
