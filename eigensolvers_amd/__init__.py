@@ -16,7 +16,9 @@ from .checkpoint import latest_checkpoint, load_checkpoint, save_checkpoint
 from .feast import feastDiagonalization
 from .lanczos import inexactLanczosDiagonalization, KrylovSpace, true_residual_norms
 from .lanczos_filter import lanczos_filter, lanczos_filter_host, lanczos_run
-from .precond_minres import csr_diagonal_host, jacobi_inverse_host, minres_jacobi_block_host, minres_jacobi_host
+from .precond_minres import (csr_diagonal_host, jacobi_inverse_host, minres_jacobi_block_host, minres_jacobi_host,
+                             minres_precond_host, separable_apply_host, separable_basis_host, separable_fit_host,
+                             separable_scale_host)
 from .precond_gcrotmk import jacobi_inverse_z_host
 from .shifted_minres import shifted_minres_host, solve_shifts
 from .subspace import (basisTransformation, find_nearest, get_pick_function_close_to_sigma,
@@ -30,5 +32,6 @@ __all__ = ["AbstractVector", "LINDEP_DEFAULT_VALUE", "HipContext", "HipCsrOperat
            "get_pick_function_maxOvlp", "shifted_minres_host", "solve_shifts",
            "lanczos_filter", "lanczos_filter_host", "lanczos_run",
            "csr_diagonal_host", "jacobi_inverse_host", "minres_jacobi_host", "minres_jacobi_block_host",
-           "jacobi_inverse_z_host"]
+           "jacobi_inverse_z_host", "minres_precond_host", "separable_apply_host", "separable_basis_host",
+           "separable_fit_host", "separable_scale_host"]
 __version__ = "0.1.0"

@@ -115,6 +115,13 @@ SIGNATURES = {
     "hipeig_csr_diagonal": [_P, _P, _P],
     "hipeig_jacobi_inverse": [_P, _I64, _P, _D, _D, _P],
     "hipeig_minres_jacobi": [_P, _P, _D, _D, _P, _P, _P, _D, C.c_int, _IP, _DP],
+    "hipeig_kron_precond_create": [_P, _P, C.c_int, _I64P, C.POINTER(_DP), C.POINTER(_DP), _PP],
+    "hipeig_kron_precond_destroy": [_P, _P],
+    "hipeig_kron_precond_info": [_P, _I64P],
+    "hipeig_kron_precond_scale": [_P, _P, _D, _D, _P],
+    "hipeig_kron_precond_transform": [_P, _P, C.c_int, C.c_int, _P, _P],
+    "hipeig_kron_precond_apply": [_P, _P, _P, _P, _P],
+    "hipeig_minres_kron_separable": [_P, _P, _P, _P, _D, _D, _P, _P, _D, C.c_int, _IP, _DP],
     "hipeig_dense_solve_small": [_P, _P, _D, _D, _D, _P, _P, _P, _P, _IP],
     "hipeig_minres_block": [_P, _P, _D, _D, C.c_int, _PP, _PP, _D, C.c_int, _IP, _DP],
     "hipeig_minres_block_jacobi": [_P, _P, _D, _D, C.c_int, _PP, _P, _PP, _D, C.c_int, _IP, _DP],

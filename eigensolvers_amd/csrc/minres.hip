@@ -27,6 +27,12 @@
 // the Lanczos vector is built from z = minv (.) r2 instead of r2 and beta^2 = <r2, z>.  z_k is materialised (a ring of
 // two), so KA gathers z_k where the plain solve gathers r2, KC also writes z_{k+1} = minv (.) y and reduces <y, z_{k+1}>,
 // and the riding KD reads z_{k-1} where the plain one shares r1.  The scalar side (minres_device.h) is unchanged.
+//
+// Separable preconditioner of a Kronecker-sum operator (opt-in through hipeig_minres_kron_separable): the
+// same PRECOND instantiations of KA and KD, which only read z.  KC is the plain instantiation (y -= (alfa/beta) r2, the
+// state update, the tests of the iteration before), followed by the 2 D mode launches of z_{k+1} = M^-1 y into the other
+// Z slot - free once the KD riding on this iteration's sweep has run - and by a reduction that puts <y, z_{k+1}> where
+// KC left <y, y>.  3 D + 3 launches per iteration; no hipGraph, no column split, no x0.
 #include <math.h>
 #include "sweep_launch.h"
 #include "minres_device.h"
@@ -34,6 +40,15 @@
 // minres_precond.hip: r2 = b, z = minv (.) b and *bz = <b, z> (synchronises; refuses <b, z> < 0)
 int hipeig_pmr_start(hipeig_ctx* c, int64_t n, const double* b, const double* minv, double* r2, double* z, int grid,
                      const MinresRed& rc, double* bz);
+// kron_precond.hip, the separable preconditioner of a Kronecker-sum operator.  hipeig_kp_start: the same
+// start with z = M^-1 b from the 2 D mode launches of an apply; hipeig_kp_apply_dot: z = M^-1 y and <y, z> into rc.tot,
+// every launch a no-op once the record `st` says done.
+struct hipeig_kron_precond;
+int hipeig_kp_start(hipeig_ctx* c, const hipeig_kron_precond* P, const double* sinv, const double* b, double* r2, double* z,
+                    int grid, const MinresRed& rc, double* bz);
+int hipeig_kp_apply_dot(hipeig_ctx* c, const hipeig_kron_precond* P, const double* sinv, const double* y, double* z, int grid,
+                        const MinresRed& rc, const MinresState* st);
+int64_t hipeig_kp_n(const hipeig_kron_precond* P);
 
 // Row epilogue of KA: v = s*src[r]; y = sign*(sigma*v - s*sum) - (beta/oldb)*r1[r]; <v,y>; and the KD of the iteration
 // before riding on this sweep.
@@ -282,8 +297,10 @@ static int minres_ka_lds_limits(const SweepPlan& p) {
 // x0 != NULL: SciPy's minres(A, b, x0) - r1 = b - A x0, the iterate starts at x0 (so ||x|| in the stopping tests
 // includes it), beta1 = ||r1||; beta1 == 0 returns x0, b == 0 returns b (scipy.sparse.linalg.minres, the x0 branch).
 // minv != NULL: the Jacobi-preconditioned solve (PRECOND kernels, one GPU, no x0).
+// sep != NULL: the separable preconditioner with its scale `minv` (then not a Jacobi inverse: only the applicator reads it).
 static int minres_solve(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign, const double* b, const double* x0,
-                        const double* minv, double* x, double rtol, int maxiter, int* info, double out_stats[8]) {
+                        const double* minv, double* x, double rtol, int maxiter, int* info, double out_stats[8],
+                        const hipeig_kron_precond* sep = nullptr) {
   HIPEIG_REQUIRE(info != nullptr, "null info");
   HIPEIG_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
   HIPEIG_REQUIRE(maxiter >= 1, "maxiter must be positive");
@@ -338,7 +355,8 @@ static int minres_solve(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign,
 
   // the first residual r2_0 in R[0] (PRECOND: and z_0 in Z[0]) and beta1^2
   if (minv) {
-    if (const int rc = hipeig_pmr_start(c, n, b, minv, R[0], Z[0], gE, redC, &bb)) return rc;
+    if (const int rc = sep ? hipeig_kp_start(c, sep, minv, b, R[0], Z[0], gE, redC, &bb)
+                           : hipeig_pmr_start(c, n, b, minv, R[0], Z[0], gE, redC, &bb)) return rc;
     if (bb == 0.0) return hipeig_vec_fill(c, x, n, 0.0);            // beta1 == 0: SciPy returns x = 0
   } else if (x0) {
     if (hipeig_spmv_shift(c, A, sigma, sign, x0, R[0])) return 1;          // A x0 with the two roundings of the lambda
@@ -371,7 +389,11 @@ static int minres_solve(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign,
   // column splits serve the slabs of row-partitioned runs, which the preconditioned solve does not take
   HIPEIG_REQUIRE(!(minv && plan.split), "the preconditioned solve does not take a column-split TCOO-W layout");
   if (const int rc = minv ? minres_ka_lds_limits<1>(plan) : minres_ka_lds_limits<0>(plan)) return rc;
-  const auto kc_kernel = minv ? minres_kc_kernel<1> : minres_kc_kernel<0>;
+  const auto kc_kernel = (minv && !sep) ? minres_kc_kernel<1> : minres_kc_kernel<0>;
+  // KC of the separable solve: the plain update (which leaves <y, y>), then z_{k+1} and <y, z_{k+1}> over it
+  auto enqueue_sep = [&](const double* yb, double* zn) -> int {
+    return sep ? hipeig_kp_apply_dot(c, sep, minv, yb, zn, gE, redC, V + 2) : 0;
+  };
   const int nPA = plan.nPA;                                  // partial <v,y> sums one iteration leaves in pA
   const bool dist = c->collectives != 0;
   MinresArgs a;
@@ -435,10 +457,11 @@ static int minres_solve(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign,
       MinresRed rc = redC;
       if (dist) rc.tot2 = hipeig_gather_slot(c, A->gl);          // travels with the NEXT exchange
       hipLaunchKernelGGL(kc_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 1, V + 2, r2, minv, yb, zn, rc, pending ? 1 : 0);
-      return 0;
+      return enqueue_sep(yb, zn);
     }
     if (enqueue_ka(src, r1, yb, V + 0, no_kd)) return 4;
     hipLaunchKernelGGL(kc_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 1, V + 2, r2, minv, yb, zn, redC, 0);
+    if (enqueue_sep(yb, zn)) return 4;
     hipLaunchKernelGGL(minres_kd_kernel, dim3(gE), dim3(HIPEIG_BLOCK), 0, c->stream, n, a, V + 2, V + 0, src, w1, w2, wn, xw, redD);
     return 0;
   };
@@ -542,6 +565,13 @@ static int minres_solve(hipeig_ctx* c, hipeig_csr* A, double sigma, double sign,
       chunk = 16;
       if (const char* e = getenv("HIPEIG_PMR_CHUNK")) chunk = atoi(e) > 0 ? atoi(e) : 16;      // tuning knob
     }
+    if (sep) {
+      // about 30 iterations of 3 D + 3 launches each (tools/kron_precond_bench.py, profiles/r22_kron_separable.jsonl): chunks of
+      // 4 / 8 / 16 -> 6.60 / 6.47 / 6.45 ms per solve at 64^3 (31 iterations), 10.83 / 10.75 / 10.73 at 100^3 (29): 4 pays for
+      // its extra looks at the record, 8 and 16 differ by less than the spread of the repetitions, so the middle value stays
+      chunk = 8;
+      if (const char* e = getenv("HIPEIG_KPMR_CHUNK")) chunk = atoi(e) > 0 ? atoi(e) : 8;      // tuning knob
+    }
     int k = 0;
     while (k < maxiter) {
       const int kend = (k + chunk < maxiter) ? k + chunk : maxiter;
@@ -591,4 +621,14 @@ extern "C" int hipeig_minres_jacobi(hipeig_ctx* c, hipeig_csr* A, double sigma, 
   HIPEIG_REQUIRE(!c->collectives, "the preconditioned solve runs on one GPU (whole vectors, no row partition)");
   HIPEIG_REQUIRE(A->nrows == A->ncols && A->row_offset == 0 && A->col_stride == 0, "the preconditioned solve needs a square operator");
   return minres_solve(c, A, sigma, sign, b, nullptr, minv, x, rtol, maxiter, info, out_stats);
+}
+
+// SciPy's minres(A, b, M=...) with the separable M^-1 = Q diag(sinv) Q^T of a Kronecker-sum operator (kron_precond.hip).
+extern "C" int hipeig_minres_kron_separable(hipeig_ctx* c, hipeig_csr* A, hipeig_kron_precond* P, const double* sinv,
+                                            double sigma, double sign, const double* b, double* x, double rtol, int maxiter,
+                                            int* info, double out_stats[8]) {
+  HIPEIG_REQUIRE(P != nullptr && sinv != nullptr, "null preconditioner");
+  HIPEIG_REQUIRE(!c->collectives, "the preconditioned solve runs on one GPU (whole vectors, no row partition)");
+  HIPEIG_REQUIRE(hipeig_kron_raw(A) != nullptr && hipeig_kp_n(P) == A->nrows, "the separable preconditioner belongs to its Kronecker-sum operator");
+  return minres_solve(c, A, sigma, sign, b, nullptr, sinv, x, rtol, maxiter, info, out_stats, P);
 }

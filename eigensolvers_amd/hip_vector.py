@@ -29,22 +29,24 @@ BLOCK_SOLVE_MIN_GCROT_LONG = 4
 PRECONDITIONER_FLOOR_DEFAULT = 1e-8      # relative; only a guard against h_ii == sigma, not a tuned value
 
 
-def _preconditioner(o, sigma=None, x0=None, ctx=None):
-    """``o["preconditioner"]`` of a ``linearSystemArgs`` dict, validated: ``None`` or ``"jacobi"``.  The key belongs to
-    the real-shift single-vector MINRES solve on one GPU; every other combination raises instead of doing something else.
-    ``o["preconditionerLockStep"]`` (``solveBlock``'s lock-step block form of that solve) is validated with it: a ``bool``,
-    and ``True`` only together with ``"preconditioner": "jacobi"``."""
+def _preconditioner(o, sigma=None, x0=None, ctx=None, H=None):
+    """``o["preconditioner"]`` of a ``linearSystemArgs`` dict, validated: ``None``, ``"jacobi"`` or ``"separable"``.  The
+    key belongs to the real-shift single-vector MINRES solve on one GPU; every other combination raises instead of doing
+    something else.  ``o["preconditionerLockStep"]`` (``solveBlock``'s lock-step block form of that solve) is validated
+    with it: a ``bool``, and ``True`` only together with ``"preconditioner": "jacobi"``.  ``"separable"`` is the
+    fast-diagonalisation preconditioner of a ``HipKronSumOperator`` (``H``, where the caller has one at hand);
+    ``o["preconditionerPotentials"]`` is validated with it: ``None`` or a list of 1-D arrays, one per mode."""
     pre = o.get("preconditioner")
     lock_step = o.get("preconditionerLockStep", False)
     if not isinstance(lock_step, (bool, np.bool_)):
         raise ValueError(f'linearSystemArgs["preconditionerLockStep"] must be a bool, got {lock_step!r}')
-    if lock_step and pre is None:
+    if lock_step and pre != "jacobi":
         raise ValueError('linearSystemArgs["preconditionerLockStep"] asks for the lock-step block form of the '
                          'preconditioned MINRES: it needs "preconditioner": "jacobi"')
     if pre is None:
         return None
-    if pre != "jacobi":
-        raise ValueError(f'linearSystemArgs["preconditioner"] must be None or "jacobi", got {pre!r}')
+    if pre not in ("jacobi", "separable"):
+        raise ValueError(f'linearSystemArgs["preconditioner"] must be None, "jacobi" or "separable", got {pre!r}')
     name = o["linearSolver"]
     if name in ("minres_shifted", "lanczos_filter"):
         raise ValueError(f'linearSystemArgs["preconditioner"] cannot be combined with linearSolver={name!r}: that path takes '
@@ -64,6 +66,19 @@ def _preconditioner(o, sigma=None, x0=None, ctx=None):
     if ctx is not None and ctx.collectives:
         raise NotImplementedError("the preconditioned MINRES runs on one GPU: a context with collectives (a row "
                                   "partition, or its HIPEIG_FORCE_COLLECTIVES rehearsal) is not implemented")
+    if pre == "separable":
+        pots = o.get("preconditionerPotentials")
+        if pots is not None:
+            if not isinstance(pots, (list, tuple)) or any(np.ndim(v) != 1 or np.iscomplexobj(v) for v in pots):
+                raise ValueError('linearSystemArgs["preconditionerPotentials"] must be None or a list of real 1-D arrays, '
+                                 f"one per mode, got {pots!r}")
+        if H is not None:
+            if not isinstance(H, HipKronSumOperator):
+                raise NotImplementedError('linearSystemArgs["preconditioner"] = "separable" diagonalises the factors of a '
+                                          f"HipKronSumOperator: {type(H).__name__} has none")
+            if pots is not None and [len(v) for v in pots] != list(H.dims):
+                raise ValueError(f'linearSystemArgs["preconditionerPotentials"] must hold one array per mode of lengths '
+                                 f"{H.dims}, got lengths {[len(v) for v in pots]}")
     return pre
 
 
@@ -823,6 +838,63 @@ class HipKronSumOperator(HipCsrOperator):
             self._diagonal = d
         return d
 
+    def _separable_tables(self, potentials=None, bases=None, eigenvalues=None):
+        """The device record of one decomposition (``hipeig_kron_precond_create``), kept per potentials: a Lanczos run
+        decomposes once.  Given ``bases`` and ``eigenvalues`` are taken as they are and not kept."""
+        from .precond_minres import separable_basis_host, separable_fit_host
+        if (bases is None) != (eigenvalues is None):
+            raise ValueError("bases and eigenvalues are given together")
+        D = len(self.dims)
+        if bases is None:
+            if potentials is None:
+                key = None
+                potentials = separable_fit_host(self._diag, self.dims)
+            else:
+                potentials = [np.ascontiguousarray(v, dtype=np.float64) for v in potentials]
+                if [v.shape for v in potentials] != [(n,) for n in self.dims]:
+                    raise ValueError(f"potentials: one 1-D array per mode of lengths {self.dims}, got shapes "
+                                     f"{[v.shape for v in potentials]}")
+                key = tuple(v.tobytes() for v in potentials)
+            cache = self.__dict__.setdefault("_separable", {})
+            if key in cache:
+                return cache[key]
+            bases, eigenvalues = separable_basis_host(self._factors, potentials)
+        else:
+            key, cache = None, None
+            bases = [np.ascontiguousarray(Q, dtype=np.float64) for Q in bases]
+            eigenvalues = [np.ascontiguousarray(lam, dtype=np.float64) for lam in eigenvalues]
+            if [Q.shape for Q in bases] != [(n, n) for n in self.dims] or [lam.shape for lam in eigenvalues] != [(n,) for n in self.dims]:
+                raise ValueError(f"bases / eigenvalues: one n_d x n_d matrix and one vector of n_d per mode of {self.dims}")
+        DP = C.POINTER(C.c_double)
+        dims = (C.c_int64 * D)(*self.dims)
+        qt = (DP * D)(*[Q.ctypes.data_as(DP) for Q in bases])
+        lt = (DP * D)(*[lam.ctypes.data_as(DP) for lam in eigenvalues])
+        h = C.c_void_p()
+        _lib.call("hipeig_kron_precond_create", self.ctx.handle, self.handle, D, dims, qt, lt, C.byref(h))
+        tables = _SeparableTables(self, h, bases, eigenvalues)
+        if cache is not None:
+            cache[key] = tables
+        return tables
+
+    def separable_preconditioner(self, sigma, floor=PRECONDITIONER_FLOOR_DEFAULT, potentials=None, bases=None,
+                                 eigenvalues=None):
+        """The fast-diagonalisation preconditioner ``M^-1 = Q S Q^T`` of ``sigma I - H``: with
+        ``H = H0 + W``, ``H0 = sum_d I (x) (T_d + diag(v_d)) (x) I`` the separable part, ``T_d + diag(v_d) = Q_d
+        diag(lam_d) Q_d^T`` decomposed once on the host, ``Q = Q_1 (x) ... (x) Q_D`` and
+        ``S = diag(1 / max(|sigma - Lam_r|, floor * max |sigma - Lam|))``, ``Lam_r = sum_d lam_d[i_d]``.  Symmetric
+        positive definite.  ``potentials``: ``None`` for the additive least-squares fit of the operator's ``V``
+        (``precond_minres.separable_fit_host``), or one 1-D array per mode.  ``bases`` and ``eigenvalues``, given together,
+        are used in place of a decomposition.  The decompositions are kept per potentials, ``sinv`` per ``(sigma, floor)``:
+        a Lanczos run builds both once.  Returns a ``SeparablePreconditioner``."""
+        tables = self._separable_tables(potentials, bases, eigenvalues)
+        key = (float(sigma), float(floor))
+        got = tables.by_shift.get(key)
+        if got is None:
+            got = tables.by_shift[key] = SeparablePreconditioner(tables, *key)
+            while len(tables.by_shift) > 2:                  # the latest shifts only: each holds a vector of N doubles
+                tables.by_shift.pop(next(iter(tables.by_shift)))
+        return got
+
     @staticmethod
     def explicit_matrix(factors, diag=None):
         """The same matrix as host CSR: ``((K_1 + K_2) + ...) + diag(V)`` with ``K_d = I (x) T_d (x) I``
@@ -892,6 +964,91 @@ class HipKronSumOperator(HipCsrOperator):
         want = (options or {}).get("reduction")
         if want not in (None, "deterministic", "fast"):
             raise ValueError(f'options["reduction"] must be "deterministic" or "fast", got {want!r}')
+
+
+class _SeparableTables:
+    """One decomposition on the device: the handle of ``hipeig_kron_precond_create`` with the host arrays it was built
+    from.  Holds the operator: its raw-sum buffer is the scratch of an apply."""
+
+    def __init__(self, H, handle, bases, eigenvalues):
+        self.H = H
+        self.ctx = H.ctx
+        self.handle = handle
+        self.bases = bases
+        self.eigenvalues = eigenvalues
+        self.by_shift = {}
+        self._finalizer = weakref.finalize(self, _SeparableTables._destroy, H.ctx, handle)
+
+    @staticmethod
+    def _destroy(ctx, handle):
+        _lib.load().hipeig_kron_precond_destroy(ctx.handle, handle)
+
+    def info(self):
+        out = (C.c_int64 * 40)()
+        _lib.call("hipeig_kron_precond_info", self.handle, out)
+        return out
+
+
+class SeparablePreconditioner:
+    """``M^-1 = Q S Q^T`` of ``HipKronSumOperator.separable_preconditioner`` for one shift and floor.  ``bases`` and
+    ``eigenvalues`` are the host arrays ``Q_d`` and ``lam_d``; everything else runs on the device."""
+
+    def __init__(self, tables, sigma, floor):
+        self._tables = tables
+        self.sigma, self.floor = sigma, floor
+        self.handle = tables.handle
+        self.ctx = tables.ctx
+        self.bases = tables.bases
+        self.eigenvalues = tables.eigenvalues
+        self._sinv = None
+
+    @property
+    def n(self):
+        return int(self._tables.info()[1])
+
+    @property
+    def launches_per_apply(self):
+        """``2 D``: the scale rides on the last forward mode."""
+        return int(self._tables.info()[2])
+
+    @property
+    def device_bytes(self):
+        """The padded tables and, once built, ``sinv``.  An apply works in the operator's raw-sum buffer and in its
+        output, so it owns no vector."""
+        return int(self._tables.info()[3]) + (0 if self._sinv is None else 8 * self.n)
+
+    def kernels(self):
+        """Per mode the form of its transform, named as in ``HipKronSumOperator.kron_info``."""
+        out = self._tables.info()
+        return [HipKronSumOperator.KERNEL_FORMS[int(out[8 + 4 * d])] for d in range(int(out[0]))]
+
+    def sinv(self):
+        """Device buffer with the diagonal of ``S``; built on first use.  ``ValueError`` where an element would not be
+        finite (``Lam_r == sigma`` with ``floor = 0``)."""
+        if self._sinv is None:
+            buf = self.ctx.alloc(self.n)
+            try:
+                _lib.call("hipeig_kron_precond_scale", self.ctx.handle, self.handle, self.sigma, self.floor, buf.ptr)
+            except _lib.HipEigError as exc:
+                if "not finite" in str(exc):
+                    raise ValueError(str(exc)) from None
+                raise
+            self._sinv = buf
+        return self._sinv
+
+    def transform(self, d, transpose, x):
+        """One mode alone (``d`` 0-based): a new device buffer with ``(I (x) Q_d (x) I) x``, ``transpose``: ``Q_d^T``."""
+        if not 0 <= int(d) < len(self.bases):
+            raise ValueError(f"mode {d} of {len(self.bases)}")
+        z = self.ctx.alloc(self.n)
+        _lib.call("hipeig_kron_precond_transform", self.ctx.handle, self.handle, int(d), 1 if transpose else 0, x.ptr, z.ptr)
+        return z
+
+    def apply(self, x):
+        """A new device buffer with ``M^-1 x``."""
+        z = self.ctx.alloc(self.n)
+        _lib.call("hipeig_kron_precond_apply", self.ctx.handle, self.handle, self.sinv().ptr, x.ptr, z.ptr)
+        return z
 
 
 class HipVector(AbstractVector):
@@ -1095,6 +1252,13 @@ class HipVector(AbstractVector):
         solve's.  ``last_solve_stats`` keeps its keys and gains ``"preconditioner": "jacobi"``.  It pays on diagonally
         dominant operators and buys nothing on others.
 
+        ``linearSystemArgs["preconditioner"] = "separable"`` (same conditions, and ``H`` a ``HipKronSumOperator`` -
+        ``NotImplementedError`` otherwise) runs the same SciPy solve with the fast-diagonalisation
+        ``M^-1 = Q S Q^T`` of ``H.separable_preconditioner``: the separable part of ``H``, the factors
+        plus 1-D potentials, inverted exactly.  ``linearSystemArgs["preconditionerPotentials"]`` is ``None`` (the additive
+        least-squares fit of the operator's ``V``) or a list of one 1-D array per mode; ``"preconditionerFloor"`` means what
+        it means for Jacobi.  ``last_solve_stats`` gains ``"preconditioner": "separable"``.
+
         ``linearSystemArgs["gcrotPreconditioner"] = "jacobi"`` (default ``None``; with ``linearSolver="gcrotmk"``, no
         ``x0``, one GPU, a whole operator - anything else raises) is the key of the GCROT solves, real shift or complex
         contour point ``z``, here and in every lock-step form of ``solveBlock``: SciPy's ``gcrotmk(A, b, M=...)`` with the
@@ -1105,7 +1269,7 @@ class HipVector(AbstractVector):
         ``"preconditioner": "jacobi"``.  DESIGN.md 3.4b says where it pays and where it does not."""
         if not isinstance(H, HipCsrOperator):
             raise TypeError("HipVector.solve needs a HipCsrOperator (device-resident CSR)")
-        pre = _preconditioner(b.options["linearSystemArgs"], sigma, x0, b.ctx)
+        pre = _preconditioner(b.options["linearSystemArgs"], sigma, x0, b.ctx, H)
         gfloor = _gcrot_preconditioner(b.options["linearSystemArgs"], x0, b.ctx, H)
         if isinstance(b, HipComplexVector):                 # HipVector(complex array) is a HipComplexVector: same entry point
             return HipComplexVector.solve(H, b, sigma, x0, opType, reverseGF)
@@ -1163,6 +1327,12 @@ class HipVector(AbstractVector):
             minv = H.jacobi_inverse(float(sigma), float(o.get("preconditionerFloor", PRECONDITIONER_FLOOR_DEFAULT)))
             _lib.call("hipeig_minres_jacobi", b.ctx.handle, H.handle, float(sigma), -1.0 if reverseGF else 1.0,
                       b._buf.ptr, minv.ptr, out.ptr, float(o["linear_tol"]), int(o["linearIter"]), C.byref(info), stats)
+        elif pre == "separable":
+            P = H.separable_preconditioner(float(sigma), float(o.get("preconditionerFloor", PRECONDITIONER_FLOOR_DEFAULT)),
+                                           potentials=o.get("preconditionerPotentials"))
+            _lib.call("hipeig_minres_kron_separable", b.ctx.handle, H.handle, P.handle, P.sinv().ptr, float(sigma),
+                      -1.0 if reverseGF else 1.0, b._buf.ptr, out.ptr, float(o["linear_tol"]), int(o["linearIter"]),
+                      C.byref(info), stats)
         elif x0 is None:
             _lib.call("hipeig_minres", b.ctx.handle, H.handle, float(sigma), -1.0 if reverseGF else 1.0,
                       b._buf.ptr, out.ptr, float(o["linear_tol"]), int(o["linearIter"]), C.byref(info), stats)

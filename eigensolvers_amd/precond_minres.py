@@ -11,6 +11,12 @@ columns of an ``[n, k]`` array with one block product per iteration, every colum
 
 ``jacobi_inverse_host`` is the NumPy statement of ``hipeig_jacobi_inverse`` and ``csr_diagonal_host`` that of
 ``hipeig_csr_diagonal``.
+
+The separable (fast-diagonalisation) preconditioner of ``HipKronSumOperator`` (``csrc/kron_precond.hip``):
+``separable_fit_host`` is the additive least-squares fit of ``V``, ``separable_basis_host`` the decompositions
+``T_d + diag(v_d) = Q_d diag(lam_d) Q_d^T``, ``separable_scale_host`` the statement of ``hipeig_kron_precond_scale``,
+``separable_apply_host`` that of ``hipeig_kron_precond_apply`` and ``minres_precond_host`` the recurrence of
+``minres_jacobi_host`` with any symmetric positive definite ``M^-1`` given as a function.
 """
 import math
 
@@ -48,14 +54,62 @@ def jacobi_inverse_host(diag, sigma, floor=1e-8):
     return 1.0 / np.maximum(t, floor_abs)
 
 
-def minres_jacobi_host(matvec, b, minv, rtol=1e-5, maxiter=None, trace=None):
-    """``scipy.sparse.linalg.minres(A, b, M=diags(minv), rtol=rtol, maxiter=maxiter)`` from ``x = 0``.
+def separable_fit_host(V, dims):
+    """The least-squares additive fit ``V ~ sum_d v_d[i_d]`` on the grid ``dims``: ``v_d[i]`` is the mean of ``V`` over all
+    other modes at ``i_d = i``, minus ``(D - 1) / D`` times the grand mean (the constant is shared evenly, which fixes the
+    one freedom of the fit).  An additive ``V`` is reproduced.  ``V = None`` gives zeros.  Returns ``D`` 1-D arrays."""
+    dims = tuple(int(n) for n in dims)
+    D = len(dims)
+    if V is None:
+        return [np.zeros(n) for n in dims]
+    V = np.asarray(V, dtype=np.float64).reshape(dims)
+    mean = float(V.mean())
+    return [V.mean(axis=tuple(e for e in range(D) if e != d)) - (D - 1) / D * mean for d in range(D)]
+
+
+def separable_basis_host(factors, potentials):
+    """``(bases, eigenvalues)``: ``numpy.linalg.eigh(T_d + diag(v_d))`` mode by mode, ``T_d + diag(v_d) = Q_d diag(lam_d)
+    Q_d^T``."""
+    bases, eigenvalues = [], []
+    for T, v in zip(factors, potentials):
+        lam, Q = np.linalg.eigh(np.asarray(T, dtype=np.float64) + np.diag(np.asarray(v, dtype=np.float64)))
+        bases.append(np.ascontiguousarray(Q))
+        eigenvalues.append(np.ascontiguousarray(lam))
+    return bases, eigenvalues
+
+
+def separable_scale_host(eigenvalues, sigma, floor=1e-8):
+    """``sinv`` of ``M^-1 = Q diag(sinv) Q^T``, flat in C order: ``Lam_r = ((lam_1[i_1] + lam_2[i_2]) + ...)``, one rounded
+    add per mode in mode order, then ``jacobi_inverse_host`` with its relative floor and its refusals."""
+    Lam = np.asarray(eigenvalues[0], dtype=np.float64)
+    for lam in eigenvalues[1:]:
+        Lam = np.add.outer(Lam, np.asarray(lam, dtype=np.float64))
+    return jacobi_inverse_host(Lam.reshape(-1), sigma, floor)
+
+
+def separable_apply_host(bases, sinv, x):
+    """``Q (sinv (.) (Q^T x))`` with ``Q = Q_1 (x) ... (x) Q_D``, mode by mode with ``np.tensordot`` in the order of the
+    device: the forward modes ``1..D`` (``Q_d^T``), the scale, the backward modes ``1..D`` (``Q_d``).  Works in the dtype
+    of ``x`` (``np.longdouble`` for the references of the tests)."""
+    dims = tuple(Q.shape[0] for Q in bases)
+    X = np.asarray(x).reshape(dims)
+    dt = X.dtype
+    for d, Q in enumerate(bases):
+        X = np.moveaxis(np.tensordot(np.asarray(Q, dtype=dt).T, X, axes=([1], [d])), 0, d)
+    X = np.asarray(sinv, dtype=dt).reshape(dims) * X
+    for d, Q in enumerate(bases):
+        X = np.moveaxis(np.tensordot(np.asarray(Q, dtype=dt), X, axes=([1], [d])), 0, d)
+    return X.reshape(-1)
+
+
+def minres_precond_host(matvec, b, apply_minv, rtol=1e-5, maxiter=None, trace=None):
+    """``scipy.sparse.linalg.minres(A, b, M=LinearOperator(apply_minv), rtol=rtol, maxiter=maxiter)`` from ``x = 0``: the
+    recurrence of ``minres_jacobi_host`` with ``z = apply_minv(r2)`` in place of ``minv * r2``.
 
     Returns ``(x, info, itn, istop)``: ``info`` is ``maxiter`` when the iteration limit was the stopping reason
     (``istop == 6``) and 0 otherwise.  ``trace``, a list, receives one record of scalars per iteration.  ``rtol`` is tested
     in SciPy's preconditioned quantities: ``beta1 = sqrt(<b, M^-1 b>)``, ``rnorm = phibar`` in the ``M^-1`` norm."""
     b = np.asarray(b, dtype=np.float64)
-    minv = np.asarray(minv, dtype=np.float64)
     n = b.shape[0]
     if maxiter is None:
         maxiter = 5 * n
@@ -63,7 +117,7 @@ def minres_jacobi_host(matvec, b, minv, rtol=1e-5, maxiter=None, trace=None):
     x = np.zeros(n)
 
     r2 = b.copy()
-    z = minv * r2                                       # start kernel
+    z = apply_minv(r2)                                  # start kernel
     beta1 = float(np.dot(r2, z))
     if beta1 < 0:
         raise ValueError("indefinite preconditioner")
@@ -98,7 +152,7 @@ def minres_jacobi_host(matvec, b, minv, rtol=1e-5, maxiter=None, trace=None):
         y = y - (alfa / beta) * r2                      # KC'
         r1 = r2
         r2 = y
-        z = minv * r2
+        z = apply_minv(r2)
         oldb = beta
         beta = float(np.dot(r2, z))
         if beta < 0:
@@ -161,6 +215,13 @@ def minres_jacobi_host(matvec, b, minv, rtol=1e-5, maxiter=None, trace=None):
 
     info = maxiter if istop == 6 else 0
     return x, info, itn, istop
+
+
+def minres_jacobi_host(matvec, b, minv, rtol=1e-5, maxiter=None, trace=None):
+    """``scipy.sparse.linalg.minres(A, b, M=diags(minv), rtol=rtol, maxiter=maxiter)`` from ``x = 0``:
+    ``minres_precond_host`` with ``z = minv * r2``."""
+    minv = np.asarray(minv, dtype=np.float64)
+    return minres_precond_host(matvec, b, lambda r: minv * r, rtol, maxiter, trace)
 
 
 def minres_jacobi_block_host(matvec_block, B, minv, rtol=1e-5, maxiter=None):

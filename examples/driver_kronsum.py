@@ -2,7 +2,8 @@
 """Shift-and-invert Lanczos for one interior state of three coupled oscillators on a direct-product sinc-DVR grid, with
 the Hamiltonian kept in its factored form  H = sum_d I (x) T_d (x) I + diag(V)  (``HipKronSumOperator``): the products run
 factor by factor on the matrix cores and the explicit matrix is never formed on the device.  The grid is small enough for
-dense ``eigh`` of the explicit matrix, which the eigenvalue is printed against."""
+dense ``eigh`` of the explicit matrix, which the eigenvalue is printed against.  ``--separable`` runs the inner MINRES solves
+with the fast-diagonalisation preconditioner of the operator (``linearSystemArgs["preconditioner"] = "separable"``)."""
 import os
 import sys
 
@@ -19,6 +20,8 @@ H = ea.HipKronSumOperator.from_factors(factors, diag=V)
 evEigh = la.eigvalsh(H.to_scipy().toarray())
 sigma = 0.513 * evEigh[3] + 0.487 * evEigh[4]                   # between two interior states
 options = {"linearSystemArgs": {"linearSolver": "minres", "linearIter": 4000, "linear_tol": 1e-10}}
+if "--separable" in sys.argv[1:]:
+    options["linearSystemArgs"]["preconditioner"] = "separable"
 Y0 = ea.HipVector(guess_vector(H.nrows, 1), options)
 ev, Y, status = ea.inexactLanczosDiagonalization(H, Y0, sigma, 8, 10, 1e-12, writeOut=False)
 exact = evEigh[ea.find_nearest(evEigh, sigma)[0]]

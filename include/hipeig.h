@@ -393,6 +393,39 @@ int hipeig_minres_jacobi(hipeig_ctx* ctx, hipeig_csr* A, double sigma, double si
                          const double* minv, double* x, double rtol, int maxiter, int* info,
                          double out_stats[8]);
 
+/* ---- separable preconditioner of the Kronecker-sum operator (opt-in: linearSystemArgs["preconditioner"] = "separable") ----
+ * SciPy's minres(A, b, M=...) again, with the fast-diagonalisation M^-1 = Q S Q^T: H = H0 + W with the separable part
+ * H0 = sum_d I (x) (T_d + diag(v_d)) (x) I, T_d + diag(v_d) = Q_d diag(lam_d) Q_d^T decomposed on the host, Q = Q_1 (x)
+ * ... (x) Q_D, S = diag(sinv), sinv_r = 1 / max(|sigma - Lam_r|, floor_rel * max |sigma - Lam|), Lam_r = sum_d lam_d[i_d].
+ * Symmetric positive definite for any orthogonal Q_d.  The reference passes no M (numpyVector.py:163).
+ *
+ * hipeig_kron_precond_create: A is the operator of hipeig_kron_create and D, dims are its own; bases[d] = Q_d on the host,
+ * n_d x n_d row-major, eigenvalues[d] = lam_d, n_d doubles.  Device copies: Q_d and Q_d^T zero-padded to a multiple of 16
+ * rows and 4 columns, as the operator's factors, and the lam_d tables.  An apply keeps no vector of its own: it works in
+ * the operator's raw-sum buffer, which is free between two products, and in its output.                            */
+typedef struct hipeig_kron_precond hipeig_kron_precond;
+int hipeig_kron_precond_create(hipeig_ctx* ctx, hipeig_csr* A, int D, const int64_t* dims, const double* const* bases,
+                               const double* const* eigenvalues, hipeig_kron_precond** out);
+int hipeig_kron_precond_destroy(hipeig_ctx* ctx, hipeig_kron_precond* P);
+/* out[0] = modes, [1] = N, [2] = launches per apply (2 D), [3] = device bytes of the tables, [4] = launches a
+ * preconditioned iteration adds to the plain one (2 D + 1); per mode d (0-based) out[8 + 4 d] = kernel form (as
+ * hipeig_kron_info), [9 + 4 d] = n_d, [10 + 4 d] / [11 + 4 d] = padded rows / columns of the device copies.       */
+int hipeig_kron_precond_info(hipeig_kron_precond* P, int64_t out[40]);
+/* sinv (device pointer, N doubles, not the operator's raw-sum buffer): Lam_r = ((lam_1[i_1] + lam_2[i_2]) + ...) in mode
+ * order, then hipeig_jacobi_inverse on it, with its refusal of an element that would not be finite.               */
+int hipeig_kron_precond_scale(hipeig_ctx* ctx, hipeig_kron_precond* P, double sigma, double floor_rel, double* sinv);
+/* one mode alone, out of place: z[o][i][j] = sum_k Q_d[i][k] x[o][k][j] (transpose != 0: Q_d[k][i]), d 0-based.   */
+int hipeig_kron_precond_transform(hipeig_ctx* ctx, hipeig_kron_precond* P, int d, int transpose, const double* x,
+                                  double* z);
+/* z = Q (sinv (.) (Q^T x)): the modes 1..D with Q_d^T, the last of them storing sinv (.) sum, then the modes 1..D with
+ * Q_d; 2 D launches.  x, z and the operator's raw-sum buffer are three different vectors; x is only read.         */
+int hipeig_kron_precond_apply(hipeig_ctx* ctx, hipeig_kron_precond* P, const double* sinv, const double* x, double* z);
+/* hipeig_minres_jacobi with this M^-1: z = M^-1 r2 from an apply per iteration, beta^2 = <r2, z>; rtol, info and
+ * out_stats as there.  One GPU, no x0, no captured graph; 3 D + 3 launches per iteration.                         */
+int hipeig_minres_kron_separable(hipeig_ctx* ctx, hipeig_csr* A, hipeig_kron_precond* P, const double* sinv,
+                                 double sigma, double sign, const double* b, double* x, double rtol, int maxiter,
+                                 int* info, double out_stats[8]);
+
 /* linearSolver = "pardiso" (numpyVector.py:166-170: spsolve of sigma*I - H, kept by the reference "only for comparing
  * with fortran" - the 4 x 4 known-answer system of unittests/test_feast_fortran.py): x = (sign*(z I - H))^-1 b by
  * Gaussian elimination with partial pivoting in the LDS of one workgroup, n <= 96, z = zr + i zi.  b_im and x_im may be
